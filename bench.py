@@ -15,8 +15,18 @@ all-reduce) per second; every one of them is also executed in the same step (MIN
 committedUpTo, the highest decided instance). Executed instances / commands per second are
 reported beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode min|classic]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode min|classic] [--full]
+                  [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it generates the inputs, fills the
+group tables, warms up, times --steps steps (one process: as hipGraph replays, --graph) and
+prints the line with metric / value / ms_per_step and the step's totals. `--full` adds what
+else the benchmark measures and checks: the enqueued pass beside the graph replay, the HIP-event
+passes around the group kernel and its roofline, the watermark checks, the bit-exact parity
+sample against the CPU oracle and the CPU baseline; the kernel benches below run only with it.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64; large
+outputs as a fixed seeded sample), the same from run to run for the same arguments.
 
 `--gpus N` (N > 1) without a launcher (no WORLD_SIZE in the environment) starts N fresh rank
 processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT), before
@@ -26,7 +36,7 @@ The default is BASELINE config 5 as written: 65,536 groups in total, strong scal
 partition over the ranks); `--scaling weak --groups G` keeps G groups per GPU instead.
 
 The other single-GPU configurations of BASELINE.json are kernel benches of their own
-(--workload; the default `step` is the headline line above):
+(--full --workload NAME; the default `step` is the headline line above):
   tally       config 2: accept tally, 16M instances x 4 replies (k_accept_tally), --mode min|classic
   prepare     config 3: CLASSIC prepare selection, 16M instances x 4 replies (k_prepare_classic)
   prepare_min config 3, MIN variant: one PrepareBookkeeping per group, G = 65,536 (k_prepare_min)
@@ -146,7 +156,25 @@ def parse():
     ap.add_argument("--replay-atomic", action="store_true",
                     help="replay: no mpx_replay_durable_reserve, so one device atomic per record "
                          "(the A/B of the binned slot maximum)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the oracle parity sample, the "
+                         "CPU baseline, the enqueued pass beside the graph replay, the per-kernel "
+                         "event passes and the roofline, and the kernel benches (--workload other "
+                         "than step). Without it a run sets up, warms up, times --steps steps and "
+                         "prints metric / value / ms_per_step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="step: after the timed steps, write what the last timed step returned "
+                         "(watermarks, totals, peerCommits, decided counts, instance states, "
+                         "Execute results, conflicts, group tables) as DIR/<name>.npy in float64; "
+                         "arrays above 2^19 elements as a fixed seeded sample")
+    a = ap.parse_args()
+    if a.workload != "step" and not a.full:
+        ap.error(f"--workload {a.workload} is one of the --full configurations: add --full")
+    if a.dump_outputs and a.workload != "step":
+        ap.error("--dump-outputs writes the outputs of the headline workload (step)")
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 class Ranks:
@@ -438,7 +466,8 @@ def step_bench(a, rk):
     steps = [batch(0, t0s, t1s), batch(1, t0s, t1s)]
     ev_done = [eng.event_create(False) for _ in range(2)]
     ev_comm = [eng.event_create(False) for _ in range(2)]
-    n_ev = max(a.steps, 1)
+    # the per-kernel event pairs belong to --full's passes and to --kernel-events inline
+    n_ev = max(a.steps, 1) if a.full or a.kernel_events == "inline" else 0
     ev_k = [(eng.event_create(), eng.event_create()) for _ in range(n_ev)]
 
     # watermark ranges other ranks own, [0, g0) and [g1, G_total) of both halves: -1 once
@@ -479,20 +508,28 @@ def step_bench(a, rk):
     for i in range(a.warmup):
         step(i, False)
     eng.synchronize()
-    rk.barrier()
-    eng.synchronize()
-    t0 = time.perf_counter()
-    for i in range(a.steps):
-        step(i, a.kernel_events == "inline")
-    t_enq = time.perf_counter() - t0  # host time to enqueue the timed steps
-    eng.synchronize()  # every stream of the device; raises if a kernel flagged an error
-    rk.barrier()
-    t1 = time.perf_counter()
-    elapsed = rk.max(t1 - t0)
+    elapsed = t_enq = None
+
+    def enqueued_pass():
+        rk.barrier()
+        eng.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            step(i, a.kernel_events == "inline")
+        t_enq = time.perf_counter() - t0  # host time to enqueue the timed steps
+        eng.synchronize()  # every stream of the device; raises if a kernel flagged an error
+        rk.barrier()
+        t1 = time.perf_counter()
+        return rk.max(t1 - t0), t_enq
+    # where the line is the graph replay's, the enqueued pass of the same steps is a comparison
+    # beside it (graph.ms_per_step_no_graph): --full
+    if a.full or not use_graph or a.kernel_events == "inline":
+        elapsed, t_enq = enqueued_pass()
     n_kev = 0
+    kern_ms = []
     if a.kernel_events == "inline":
         kern_ms = [eng.event_elapsed_ms(e0, e1) for e0, e1 in ev_k[:a.steps]]
-    else:
+    elif a.full:
         # the kernel times from a separate pass of the same steps right after the timed region:
         # timing events between the kernels of every timed step cost the enqueued step ~17 us
         # (a timestamp write on the compute stream per event; --emulate-world 8: 0.117-0.120 ms
@@ -517,7 +554,8 @@ def step_bench(a, rk):
         # a second U-step graph, the same steps with a HIP event pair around each group kernel
         # (external event nodes, which cost a replay a few us per step, so the timed graphs have
         # none): replayed once after the timed region, it gives the roofline's kernel times
-        ev_g = [(eng.event_create(), eng.event_create()) for _ in range(U)]
+        # (--full)
+        ev_g = [(eng.event_create(), eng.event_create()) for _ in range(U if a.full else 0)]
 
         def capture(n, evs=False):
             eng.graph_begin(comp)
@@ -532,11 +570,14 @@ def step_bench(a, rk):
                 raise
             graph_info = {"used": False, "unavailable": str(e)[:160]}
             use_graph = False
-        if use_graph:
+        if use_graph and a.full:
             try:
                 g_ev = capture(U, evs=True)
             except MpxError:  # (a runtime without external event nodes: the enqueued pass's)
                 g_ev = None
+    if elapsed is None and not use_graph:  # no stream capture after all: the enqueued steps
+        elapsed, t_enq = enqueued_pass()
+        last = (a.steps - 1) & 1
     if use_graph:
         for _ in range(max(a.warmup, 1)):
             eng.graph_launch(graphs[U], comp)
@@ -553,8 +594,8 @@ def step_bench(a, rk):
         graph_info = {"used": True, "steps_per_graph": U, "graph_launches": len(chunks),
                       "collective_stream": "compute (in the graph)",
                       "ms_per_step_graph": elapsed_graph / a.steps * 1e3,
-                      "ms_per_step_no_graph": elapsed / a.steps * 1e3,
-                      "kernel_ms_median_enqueued": float(np.median(kern_ms))}
+                      "ms_per_step_no_graph": elapsed / a.steps * 1e3 if elapsed else None,
+                      "kernel_ms_median_enqueued": float(np.median(kern_ms)) if kern_ms else None}
         if g_ev is not None:
             for _ in range(3):  # (the first replays of a fresh graph run cold)
                 eng.graph_launch(g_ev, comp)
@@ -564,7 +605,7 @@ def step_bench(a, rk):
                                           "event pair around each group kernel")
             graph_info["evented_replay_steps"] = 3 * U
             eng.graph_destroy(g_ev)
-        else:
+        elif a.full:
             graph_info["kernel_times"] = "the enqueued pass's events"
         last = ((U if g_ev is not None else chunks[-1]) - 1) & 1  # the last replayed step
         elapsed = elapsed_graph
@@ -574,52 +615,94 @@ def step_bench(a, rk):
     # ---- outputs of the (identical) timed steps -------------------------------------------------
     tot = ar.get(d["tot"][last])  # summed over ranks by the step's all-reduce
     n_decided, n_exec_inst, n_exec_cmds = (int(x) for x in tot)
-    wm = ar.get(d["wmr"][last])
-    committed, executed = wm[:G_total], wm[G_total:]
-    own_e = executed[g0:g1].astype(np.int64)
-    kc = ar.get(d["kc1"])
-    # every rank sees every group's watermark (no -1 or poison left) and all ranks hold the
-    # same vector after the all-reduce; an emulated rank holds its own range and -1 elsewhere
-    if emu:
-        foreign = np.ones(G_total, bool)
-        foreign[g0:g1] = False
-        wm_ok = bool((committed[g0:g1] >= 0).all() and (executed[g0:g1] < ipg).all()
-                     and (committed[g0:g1] < ipg).all() and (committed[foreign] == -1).all()
-                     and (executed[foreign] == -1).all())
-    else:
-        wm_ok = bool((committed >= 0).all() and (wm < ipg).all())
-    import hashlib
-    wm_sha = hashlib.sha256(wm.tobytes()).hexdigest()
-    shas = rk.gather(wm_sha)
-    coff = b["cmd_off"].astype(np.int64)
-    gidx = np.arange(G, dtype=np.int64) * ipg
-    own_cmds = int((coff[gidx + own_e + 1] - coff[gidx]).sum())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, d, ar, last, G, G_total, g0, ipg, N, K)
 
-    # algorithmic bytes of one group-step launch (this rank): replies + instance state in/out,
-    # executed commands (op,key,val in; ret,conf out), group table in/out, per-group scalars
-    n_rec = len(b["recs"])
-    alg = (n_rec * 16 + G * ipg * 16 * 2 + own_cmds * (17 + 9)
-           + int(kc.sum()) * 16 * 2 + G * (4 * 4 + 2 * N * 4 + 4 * 2 + 8 * 2 + 4))
-    kern_avg_ms = float(np.mean(kern_ms)) if kern_ms else float("nan")
-    kern_med_ms = float(np.median(kern_ms)) if kern_ms else float("nan")
-    # the kernel's time is bounded from above by its event bracket (the kernel plus the dispatch
-    # on either side and the event nodes' own cost) and by the step it is part of (the kernel
-    # plus the work-list kernel and the collective): achieved from the tighter bound, so the
-    # kernel is never credited with more time than the step took (the bracket came out 0.2 %
-    # above ms_per_step on one box)
-    step_ms = elapsed / max(a.steps, 1) * 1e3
-    kern_bound_ms = min(kern_avg_ms, step_ms)
-    achieved_gbs = alg / (kern_bound_ms * 1e-3) / 1e9
-    tkey = {"workload": "step", "mode": a.mode, "groups": G, "ipg": ipg, "replicas": N,
-            "cmds": B, "keys": a.keys, "kv_per_group": K}
-    traffic, tnote = traffic_for(tkey, alg, a.traffic_json)
+    def full_fields():
+        """--full: the watermark checks, the roofline of the group kernel, the oracle parity
+        sample and the CPU baseline (every rank calls it: the checks gather over the ranks)"""
+        wm = ar.get(d["wmr"][last])
+        committed, executed = wm[:G_total], wm[G_total:]
+        own_e = executed[g0:g1].astype(np.int64)
+        kc = ar.get(d["kc1"])
+        # every rank sees every group's watermark (no -1 or poison left) and all ranks hold the
+        # same vector after the all-reduce; an emulated rank holds its own range and -1 elsewhere
+        if emu:
+            foreign = np.ones(G_total, bool)
+            foreign[g0:g1] = False
+            wm_ok = bool((committed[g0:g1] >= 0).all() and (executed[g0:g1] < ipg).all()
+                         and (committed[g0:g1] < ipg).all() and (committed[foreign] == -1).all()
+                         and (executed[foreign] == -1).all())
+        else:
+            wm_ok = bool((committed >= 0).all() and (wm < ipg).all())
+        import hashlib
+        wm_sha = hashlib.sha256(wm.tobytes()).hexdigest()
+        shas = rk.gather(wm_sha)
+        coff = b["cmd_off"].astype(np.int64)
+        gidx = np.arange(G, dtype=np.int64) * ipg
+        own_cmds = int((coff[gidx + own_e + 1] - coff[gidx]).sum())
 
-    res = {}
-    if rank == 0:
-        # parity: the first groups of the timed output against the oracle (test infra)
-        res["parity"] = parity_sample(b, d, ar, a, mode, N, K, G_total, g0, last)
+        # algorithmic bytes of one group-step launch (this rank): replies + instance state
+        # in/out, executed commands (op,key,val in; ret,conf out), group table in/out,
+        # per-group scalars
+        n_rec = len(b["recs"])
+        alg = (n_rec * 16 + G * ipg * 16 * 2 + own_cmds * (17 + 9)
+               + int(kc.sum()) * 16 * 2 + G * (4 * 4 + 2 * N * 4 + 4 * 2 + 8 * 2 + 4))
+        kern_avg_ms = float(np.mean(kern_ms)) if kern_ms else float("nan")
+        kern_med_ms = float(np.median(kern_ms)) if kern_ms else float("nan")
+        # the kernel's time is bounded from above by its event bracket (the kernel plus the
+        # dispatch on either side and the event nodes' own cost) and by the step it is part of
+        # (the kernel plus the work-list kernel and the collective): achieved from the tighter
+        # bound, so the kernel is never credited with more time than the step took (the bracket
+        # came out 0.2 % above ms_per_step in one run, DESIGN §6)
+        step_ms = elapsed / max(a.steps, 1) * 1e3
+        kern_bound_ms = min(kern_avg_ms, step_ms)
+        achieved_gbs = alg / (kern_bound_ms * 1e-3) / 1e9
+        tkey = {"workload": "step", "mode": a.mode, "groups": G, "ipg": ipg, "replicas": N,
+                "cmds": B, "keys": a.keys, "kv_per_group": K}
+        traffic, tnote = traffic_for(tkey, alg, a.traffic_json)
+        if rank != 0:
+            return {}
+        out = {
+            "roofline": {
+                "bound": "hbm", "kernel": "k_group_fast", "achieved": achieved_gbs,
+                "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved_gbs / PEAK_HBM_GBS,
+                "traffic": traffic, "traffic_note": tnote, "traffic_key": tkey,
+                "traffic_kernels": ["k_group_fast"],
+                "alg_bytes_per_launch": alg,
+                "alg_table_bytes": int(kc.sum()) * 16 * 2,
+                "alg_note": ("replies 16 B + instance state 16 B in + 16 B out, executed commands "
+                             "17 B in + 9 B out, per-group scalars, and the group KV tables 16 B "
+                             "per live key in + out (the step re-reads its unchanged table: "
+                             "alg_table_bytes of the total)"),
+                "kernel_ms_avg": kern_avg_ms, "kernel_ms_median": kern_med_ms,
+                "kernel_ms_min": float(np.min(kern_ms)),
+                "kernel_ms_bound": kern_bound_ms,
+                "frac_at_median": alg / (min(kern_med_ms, step_ms) * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                "timing": ("HIP events recorded by the engine right before and after each "
+                           "k_group_fast launch (mpx_group_step_events) on the compute stream - "
+                           "in a replay of the timed hipGraph (external event nodes) when the "
+                           "line is the graph pass, as ms_per_step is, else in an enqueued pass "
+                           "of the same steps right after the timed region (--kernel-events); "
+                           + ("one launch per step: the kernel's last workgroup folds the step "
+                              "totals inside the bracket" if one_launch else
+                              "the work-list kernel (second launch) is outside")
+                           + "; the collective is outside; achieved from kernel_ms_bound = "
+                           "min(their mean, ms_per_step) - both bound the kernel's time from "
+                           "above - the median beside it (SURVEY 8(d))"),
+                "launches_per_step": 1 if one_launch else 2,
+            },
+            "enqueue_ms_per_step": t_enq / max(a.steps, 1) * 1e3,  # the enqueued pass's host time
+            "watermark_allreduce_ok": wm_ok,
+            "watermarks_sha256": wm_sha,
+            "watermarks_identical_on_all_ranks": len(set(shas)) == 1,
+            # parity: the first groups of the timed output against the oracle (test infra)
+            "parity": parity_sample(b, d, ar, a, mode, N, K, G_total, g0, last),
+        }
         if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(b, a, mode, N, K)
+            out["cpu_baseline"] = cpu_baseline(b, a, mode, N, K)
+        return out
+    full = full_fields() if a.full else {}
 
     if rank == 0:
         cfg_work = (f"config5: {G_total} groups ({a.scaling} scaling, {G} on rank 0) x {ipg} "
@@ -653,35 +736,6 @@ def step_bench(a, rk):
                                   "on a second stream overlapping the next step's kernel")),
             },
             "value_counts": "instances decided by the step (quorum crossings), all ranks",
-            "roofline": {
-                "bound": "hbm", "kernel": "k_group_fast", "achieved": achieved_gbs,
-                "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved_gbs / PEAK_HBM_GBS,
-                "traffic": traffic, "traffic_note": tnote, "traffic_key": tkey,
-                "traffic_kernels": ["k_group_fast"],
-                "alg_bytes_per_launch": alg,
-                "alg_table_bytes": int(kc.sum()) * 16 * 2,
-                "alg_note": ("replies 16 B + instance state 16 B in + 16 B out, executed commands "
-                             "17 B in + 9 B out, per-group scalars, and the group KV tables 16 B "
-                             "per live key in + out (the step re-reads its unchanged table: "
-                             "alg_table_bytes of the total)"),
-                "kernel_ms_avg": kern_avg_ms, "kernel_ms_median": kern_med_ms,
-                "kernel_ms_min": float(np.min(kern_ms)),
-                "kernel_ms_bound": kern_bound_ms,
-                "frac_at_median": alg / (min(kern_med_ms, step_ms) * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                "timing": ("HIP events recorded by the engine right before and after each "
-                           "k_group_fast launch (mpx_group_step_events) on the compute stream - "
-                           "in a replay of the timed hipGraph (external event nodes) when the "
-                           "line is the graph pass, as ms_per_step is, else in an enqueued pass "
-                           "of the same steps right after the timed region (--kernel-events); "
-                           + ("one launch per step: the kernel's last workgroup folds the step "
-                              "totals inside the bracket" if one_launch else
-                              "the work-list kernel (second launch) is outside")
-                           + "; the collective is outside; achieved from kernel_ms_bound = "
-                           "min(their mean, ms_per_step) - both bound the kernel's time from "
-                           "above - the median beside it (SURVEY 8(d))"),
-                "launches_per_step": 1 if one_launch else 2,
-            },
-            "enqueue_ms_per_step": t_enq / max(a.steps, 1) * 1e3,  # the enqueued pass's host time
             "decided_instances_per_step": n_decided,
             "executed_instances_per_step": n_exec_inst,
             "executed_commands_per_step": n_exec_cmds,
@@ -689,11 +743,10 @@ def step_bench(a, rk):
             "executed_instances_per_s": n_exec_inst * a.steps / elapsed,
             "executed_commands_per_s": n_exec_cmds * a.steps / elapsed,
             # table fill + warm-up + timed (+ the graph replays' warm-up and timed steps)
-            "launches_in_process": 1 + a.warmup + a.steps + n_kev + (
+            "launches_in_process": 1 + a.warmup + (0 if t_enq is None else a.steps) + n_kev + (
                 max(a.warmup, 1) * graph_info["steps_per_graph"] + a.steps
                 + graph_info.get("evented_replay_steps", 0) if use_graph else 0),
             "graph": graph_info or {"used": False},
-            "watermark_allreduce_ok": wm_ok,
             **({"emulated_world": {
                 "ranks": emu, "groups_on_this_rank": G, "groups_total": G_total,
                 "per_rank_value": n_decided * a.steps / elapsed,
@@ -702,12 +755,10 @@ def step_bench(a, rk):
                          "= P x the per-rank rate, assuming every rank runs as fast and the "
                          "overlapped all-reduce over xGMI stays hidden: a proxy, not a "
                          "multi-GPU measurement")}} if emu else {}),
-            "watermarks_sha256": wm_sha,
-            "watermarks_identical_on_all_ranks": len(set(shas)) == 1,
             "gen_s": round(t_gen, 2),
             "runtime": _lib.runtime_info(),
         }
-        line.update(res)
+        line.update(full)
         print(json.dumps(line), flush=True)
     if comm != comp:
         eng.stream_destroy(comm)
@@ -772,6 +823,56 @@ def parity_sample(b, d, ar, a, mode, N, K, G_total, g0, last):
 def _as(x, dtype):
     """the same device buffer viewed with another element type"""
     return DevArray(x.ptr, x.nbytes, dtype, (x.nbytes // np.dtype(dtype).itemsize,))
+
+
+DUMP_SAMPLE = 1 << 19  # elements (instances, commands, table slots) kept of a larger output
+
+
+def dump_outputs(path, d, ar, last, G, G_total, g0, ipg, N, K):
+    """--dump-outputs: what the last timed step returned to its caller, one float64 .npy per
+    output (every value of this workload - instance numbers, ballots, counts, keys < 2^32 and
+    values = command indices - is an integer below 2^53, so float64 holds it exactly; checked).
+    Outputs above DUMP_SAMPLE elements are sampled at fixed seeded indices, written beside them
+    as instance_index / command_index / kv_slot_index; group-table slots at or past the group's
+    key count are not output of the step and are written as 0. 48 MB at the default shape."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20240611)
+
+    def sample(name, n):
+        if n <= DUMP_SAMPLE:
+            return None
+        idx = np.unique(rng.integers(0, n, DUMP_SAMPLE))
+        write(name, idx)
+        return idx
+
+    def write(name, x):
+        x = np.asarray(x)
+        assert x.size == 0 or np.abs(x.astype(np.int64)).max() < 1 << 53, name
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float64))
+
+    def sampled(name, x, idx, width=1):
+        x = x.reshape(-1, width) if width > 1 else x
+        write(name, x if idx is None else x[idx])
+
+    wm = ar.get(d["wmr"][last])
+    write("committed_up_to", wm[g0:g0 + G])
+    write("executed_up_to", wm[G_total + g0:G_total + g0 + G])
+    write("step_totals", ar.get(d["tot"][last]))
+    write("peer_commits", ar.get(d["po"]))
+    write("n_decided", ar.get(d["nd"]))
+    kc = ar.get(d["kc1"]).astype(np.int64)
+    write("kv_cnt", kc)
+    sampled("st_out", ar.get(_as(d["st_out"], np.int32)), sample("instance_index", G * ipg), 4)
+    ci = sample("command_index", d["ret"].size)
+    sampled("ret", ar.get(d["ret"]), ci)
+    sampled("conf_prev", ar.get(d["conf"]), ci)
+    si = sample("kv_slot_index", G * K)
+    slot = np.arange(G * K, dtype=np.int64) if si is None else si
+    dead = slot[(slot % K) >= kc[slot // K]]
+    for name, buf in (("kv_key", d["kk1"]), ("kv_val", d["kv1"])):
+        x = ar.get(buf)
+        x[dead] = 0
+        sampled(name, x, si)
 
 
 def cpu_baseline(b, a, mode, N, K):

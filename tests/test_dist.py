@@ -127,14 +127,17 @@ def test_strong_scaling_partition_covers_groups():
 
 
 # ---- bench.py --gpus N: the launcher and the engine's multi-rank step (nranks > 1) ----------
-def _bench(stub_lib, *args, devices=2, timeout=240):
+def _bench(stub_lib, *args, devices=2, timeout=240, full=True):
+    """bench.py over the stub library; --full unless told otherwise: the tests below read the
+    parity, watermark and roofline fields, which a plain run leaves out"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MPX_LIB=stub_lib, MPX_STUB_DEVICES=str(devices))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    return subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args],
+    return subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args,
+                           *(["--full"] if full else [])],
                           capture_output=True, text=True, env=env, timeout=timeout, cwd=root)
 
 
@@ -246,3 +249,94 @@ def test_bench_emulate_world(stub_lib, P, g_total):
     assert 0 < emu["groups_on_this_rank"] < g_total
     assert line["watermark_allreduce_ok"] and line["parity"]["bit_exact"], line["parity"]
     assert "EMULATED" in line["config"]["workload"]
+
+
+def test_bench_plain_run_and_dump_outputs(stub_lib, tmp_path):
+    """a plain run (no --full) prints the headline fields and none of what --full adds;
+    --dump-outputs writes the last timed step's outputs as float64 arrays, the same from run to
+    run, equal to the oracle's steady-state step over the same groups"""
+    import json
+
+    from oracle_lib import Oracle
+    outs = []
+    for name in ("a", "b"):
+        r = _bench(stub_lib, "--gpus", "1", "--groups-total", "16", "--steps", "3", "--warmup",
+                   "1", "--dump-outputs", str(tmp_path / name), devices=1, full=False)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        outs.append({f[:-4]: np.load(tmp_path / name / f)
+                     for f in sorted(os.listdir(tmp_path / name))})
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "instances/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "int32/int64" and line["metric"].startswith("decided+applied")
+    assert line["value"] == pytest.approx(
+        line["decided_instances_per_step"] / (line["ms_per_step"] * 1e-3))
+    assert not {"parity", "cpu_baseline", "roofline", "watermarks_sha256"} & set(line)
+    a, b = outs
+    assert sorted(a) == sorted(b) and all(a[k].dtype == np.float64 for k in a)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    full = synth.group_batch(16, 256, 5, 4, 256, p_ok=0.7, p_put=0.5, seed=45)
+    o = Oracle(5, R.MODE_MIN, kv_per_group=256)
+    w0 = o.group_step(full)
+    want = o.group_step(full, w0["kv_cnt"], w0["kv_key"], w0["kv_val"])
+    for name, key in (("committed_up_to", "committed_out"), ("executed_up_to", "executed_out"),
+                      ("peer_commits", "peer_out"), ("n_decided", "n_decided"),
+                      ("kv_cnt", "kv_cnt"), ("ret", "ret"), ("conf_prev", "conf_prev")):
+        assert np.array_equal(a[name], want[key].astype(np.float64)), name
+    assert np.array_equal(a["st_out"], want["st_out"].view(np.int32).reshape(-1, 4))
+    assert a["step_totals"][0] == want["n_decided"].sum() == line["decided_instances_per_step"]
+    live = (np.arange(16 * 256) % 256) < np.repeat(want["kv_cnt"].astype(np.int64), 256)
+    for name in ("kv_key", "kv_val"):
+        assert np.array_equal(a[name][live], want[name][live].astype(np.float64)), name
+        assert not a[name][~live].any()
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path):
+    """outputs above bench.DUMP_SAMPLE elements are written as a fixed sample with its indices,
+    the same indices on every call; table slots past a group's key count come out as 0"""
+    import bench
+    G, ipg, N, K = 2049, 256, 5, 256  # G * ipg and G * K just above the sample size
+    m = G * ipg * 4
+    rng = np.random.default_rng(7)
+    host = {}
+
+    class Buf:
+        def __init__(self, x):
+            self.ptr, self.nbytes, self.dtype, self.size = len(host) + 1, x.nbytes, x.dtype, x.size
+            host[self.ptr] = x
+
+    class FakeArena:
+        def get(self, d):
+            return host[d.ptr].view(d.dtype).copy()
+    kc = rng.integers(0, K + 1, G).astype(np.uint32)
+    d = dict(wmr=[Buf(rng.integers(-1, ipg, 2 * G).astype(np.int32))] * 2,
+             tot=[Buf(np.array([5, 6, 7], np.int64))] * 2,
+             po=Buf(rng.integers(0, ipg, G * N).astype(np.int32)),
+             nd=Buf(rng.integers(0, ipg, G).astype(np.uint32)), kc1=Buf(kc),
+             st_out=Buf(rng.integers(-9, 9, G * ipg * 4).astype(np.int32)),
+             ret=Buf(rng.integers(0, m, m)), conf=Buf(rng.integers(0, 2, m).astype(np.uint8)),
+             kk1=Buf(rng.integers(1, K, G * K)), kv1=Buf(rng.integers(1, m, G * K)))
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), d, FakeArena(), 0, G, G, 0, ipg, N, K)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    total = 0
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    out = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for name, src, width, index in (("st_out", "st_out", 4, "instance_index"),
+                                    ("ret", "ret", 1, "command_index"),
+                                    ("conf_prev", "conf", 1, "command_index")):
+        idx = out[index].astype(np.int64)
+        assert 0 < len(idx) <= bench.DUMP_SAMPLE and (np.diff(idx) > 0).all()
+        ref = host[d[src].ptr].reshape(-1, width)[idx] if width > 1 else host[d[src].ptr][idx]
+        assert np.array_equal(out[name], ref), name
+    idx = out["kv_slot_index"].astype(np.int64)
+    live = (idx % K) < kc[idx // K]
+    assert np.array_equal(out["kv_val"], np.where(live, host[d["kv1"].ptr][idx], 0))
+    assert np.array_equal(out["kv_key"], np.where(live, host[d["kk1"].ptr][idx], 0))

@@ -12,12 +12,12 @@ if [ -n "${PYTEST_K:-}" ]; then
 fi
 for d in ${DISTS:-uniform zipf}; do
   if [ -n "${STAMP_LIB:-}" ]; then
-    MPX_LIB=$PWD/$STAMP_LIB timeout -k 10 300 python bench.py --workload apply --dist $d --steps 2 --warmup 0 --no-cpu-baseline > $OUT/stamp_$d.log 2>&1
+    MPX_LIB=$PWD/$STAMP_LIB timeout -k 10 300 python bench.py --full --workload apply --dist $d --steps 2 --warmup 0 --no-cpu-baseline > $OUT/stamp_$d.log 2>&1
     rc=$?; echo "stamp $d rc=$rc"; grep _STAMP $OUT/stamp_$d.log | tail -3; [ $rc = 0 ] || exit $rc
   fi
   for lib in ${PROF_LIBS:-}; do
     n=$(basename $lib .so)_$d
-    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --workload apply --dist $d --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
+    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --full --workload apply --dist $d --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
     rc=$?; echo "prof $n rc=$rc"; [ $rc = 0 ] || exit $rc
     python3 tools/trace_calls.py $OUT/prof_$n/t_kernel_trace.csv k_ap | tail -6
   done

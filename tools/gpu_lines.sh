@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/lines_${TAG:-r03}; mkdir -p $OUT
 run() {
   name=$1; shift
-  timeout -k 10 ${BT:-300} python bench.py "$@" > $OUT/$name.log 2>&1
+  timeout -k 10 ${BT:-300} python bench.py --full "$@" > $OUT/$name.log 2>&1
   rc=$?; echo "$name rc=$rc"; grep '^{' $OUT/$name.log | tail -1 | cut -c1-160
   [ $rc = 0 ] || exit $rc
 }

@@ -8,7 +8,7 @@ OUT=gpurun_out/profcfg_${TAG:-r01}
 mkdir -p $OUT
 run() {
   name=$1; shift
-  timeout -k 10 ${BT:-400} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- python3 bench.py "$@" > $OUT/$name.log 2>&1
+  timeout -k 10 ${BT:-400} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- python3 bench.py --full "$@" > $OUT/$name.log 2>&1
   rc=$?; echo "$name rc=$rc"; grep '^{' $OUT/$name.log | tail -1 | cut -c1-400
   case $rc in 0) ;; *) exit $rc;; esac
 }

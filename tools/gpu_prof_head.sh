@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 TAG=${TAG:-r03}
 OUT=gpurun_out/head_$TAG
 mkdir -p $OUT
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $OUT/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; grep '^{' $OUT/bench.log | cut -c1-300; [ $rc = 0 ] || exit $rc
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; [ $rc = 0 ] || exit $rc
 timeout -k 10 900 python tools/pmc_collect.py --out gpurun_out/pmc_$TAG/traffic.json "$@"
 rc=$?; echo "pmc rc=$rc"; exit $rc

@@ -15,6 +15,6 @@ IFS=';' read -ra SETS <<< "${BENCHES:-}"
 for args in "${SETS[@]}"; do
   [ -z "${args// }" ] && continue
   i=$((i+1))
-  timeout -k 10 ${BT:-300} python bench.py $args > $OUT/b$i.log 2>&1
+  timeout -k 10 ${BT:-300} python bench.py --full $args > $OUT/b$i.log 2>&1
   rc=$?; echo "b$i [$args] rc=$rc"; grep '^{' $OUT/b$i.log | tail -1 | cut -c1-160; [ $rc = 0 ] || exit $rc
 done

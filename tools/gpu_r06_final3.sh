@@ -9,7 +9,7 @@ rc=$?; grep -E "rc=|passed|failed" gpurun_out/check_r06c.txt | tail -5; [ $rc = 
 grep -q "smoke rc=0" gpurun_out/check_r06c.txt || exit 1
 grep -qE "[0-9]+ failed" gpurun_out/pytest_gpu.log && exit 1
 OUT=gpurun_out/head_r06c; mkdir -p $OUT
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $OUT/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; grep '^{' $OUT/bench.log | cut -c1-300; [ $rc = 0 ] || exit $rc
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; exit $rc

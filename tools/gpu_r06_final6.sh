@@ -8,5 +8,6 @@ rc=$?; grep -E "rc=|passed|failed" gpurun_out/check_r06g.txt | tail -4; [ $rc = 
 grep -q "smoke rc=0" gpurun_out/check_r06g.txt || exit 1
 grep -qE "[0-9]+ failed" gpurun_out/pytest_gpu.log && exit 1
 mkdir -p gpurun_out/r06_f7
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > gpurun_out/r06_f7/headline.log 2>&1
+OUT=$_  # the folder made above
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $OUT/headline.log 2>&1
 rc=$?; echo "bench rc=$rc"; grep '^{' gpurun_out/r06_f7/headline.log | cut -c1-200; exit $rc

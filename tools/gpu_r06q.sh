@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_decode.py tests/test_gpu_fuzz.p
 rc=$?; echo "pytest rc=$rc"; tail -1 $OUT/pytest.log; [ $rc = 0 ] || exit $rc
 for lib in minpaxos_amd/libmpx.so minpaxos_amd/ab/libmpx_decpad0.so; do
   n=$(basename $lib .so)
-  MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --workload decode --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
+  MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --full --workload decode --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
   rc=$?; echo "prof $n rc=$rc"; [ $rc = 0 ] || exit $rc
   python3 tools/trace_calls.py $OUT/prof_$n/t_kernel_trace.csv k_dec | tail -8
 done

@@ -11,7 +11,7 @@ i=0
 for m in min classic; do
   for lib in minpaxos_amd/libmpx.so minpaxos_amd/ab/libmpx_prmark.so minpaxos_amd/libmpx.so minpaxos_amd/ab/libmpx_prmark.so; do
     i=$((i+1)); n=$(basename $lib .so)_${m}_$i
-    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --workload stream --mode $m --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
+    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --full --workload stream --mode $m --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
     rc=$?; echo "prof $n rc=$rc"; [ $rc = 0 ] || exit $rc
     python3 tools/trace_calls.py $OUT/prof_$n/t_kernel_trace.csv k_sd | tail -9
   done

@@ -11,7 +11,7 @@ i=0
 for d in "" "--replay-dups"; do
   for lib in minpaxos_amd/libmpx.so ${OLD:-minpaxos_amd/ab/libmpx_rpold.so} minpaxos_amd/libmpx.so ${OLD:-minpaxos_amd/ab/libmpx_rpold.so}; do
     i=$((i+1)); n=$(basename $lib .so)${d:+_dups}_$i
-    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --workload replay $d --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
+    MPX_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -o t -- python3 bench.py --full --workload replay $d --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_$n.log 2>&1
     rc=$?; echo "prof $n rc=$rc"; [ $rc = 0 ] || exit $rc
     python3 -c "
 import csv,sys

@@ -11,7 +11,7 @@ done
 for v in "" "--no-overlap"; do
   for lib in minpaxos_amd/libmpx.so minpaxos_amd/ab/libmpx_pm.so; do
     n=p8$(echo $v | tr -d ' -')_$(basename $lib .so)
-    MPX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --emulate-world 8 --graph on --steps 64 --warmup 3 --no-cpu-baseline $v > $OUT/$n.log 2>&1
+    MPX_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --emulate-world 8 --graph on --steps 64 --warmup 3 --no-cpu-baseline $v > $OUT/$n.log 2>&1
     rc=$?; [ $rc = 0 ] || { echo "$n rc=$rc"; exit $rc; }
     python3 -c "import json; d=[json.loads(l) for l in open('$OUT/$n.log') if l.startswith('{')][-1]; print('$n', round(d['ms_per_step'],4), round(d['roofline']['kernel_ms_median'],4))"
   done

@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def bench_line(args, extra=()):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args.split(),
-                        "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=600,
+                        "--full", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=600,
                        cwd=ROOT)
     if r.returncode:
         raise SystemExit(f"bench {args}: rc {r.returncode}\n{r.stderr[-2000:]}")
@@ -38,7 +38,7 @@ def pmc_pass(args, counter, d, steps):
     cmd = ["timeout", "-s", "KILL", "300", "rocprofv3", "--pmc", *counter.split(","),
            "--output-format", "csv",
            "-d", d, "-o", "pmc", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-           *args.split(), "--no-cpu-baseline", "--steps", str(steps), "--warmup", "1"]
+           *args.split(), "--full", "--no-cpu-baseline", "--steps", str(steps), "--warmup", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     if r.returncode:
         raise SystemExit(f"pmc {counter} {args}: rc {r.returncode}\n{r.stderr[-2000:]}")

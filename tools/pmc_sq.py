@@ -30,7 +30,7 @@ GROUPS = [
 def run_pass(args, counters, d):
     cmd = ["timeout", "-s", "KILL", "400", "rocprofv3", "--pmc", *counters.split(","),
            "--output-format", "csv", "-d", d, "-o", "pmc", "--", sys.executable,
-           os.path.join(ROOT, "bench.py"), *args.split(), "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), *args.split(), "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     if r.returncode:
         print(f"pmc {counters}: rc {r.returncode}\n{r.stderr[-1500:]}", file=sys.stderr, flush=True)
