@@ -29,6 +29,10 @@
  *                              src/bareminpaxos/bareminpaxos.go:1030-1042 and executeCommands
  *                            :1076-1084 through ReplyProposeTS (genericsmr.go:529-535): the byte
  *                            run each client connection receives for a batch of replies
+ *   mpx_accept_handle     <- bareminpaxos.(*Replica).handleAccept  bareminpaxos.go:753-806 /
+ *                            paxos.(*Replica).handleAccept  src/paxos/paxos.go:470-520: the
+ *                            acceptor's half of Phase 2, and mpx_encode_accept_replies the
+ *                            AcceptReply frames replyAccept writes to each leader's connection
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -75,7 +79,8 @@ extern "C" {
 
 #define MPX_ABI_VERSION 8  /* 4: + mpx_group_step_totals_dev; 5: + mpx_graph_*, mpx_apply_buffers / _staged;
                               6: + mpx_replay_durable_reserve; 7: + mpx_group_step_events;
-                              8: + MPX_FLAG_STEP_ONE_LAUNCH */
+                              8: + MPX_FLAG_STEP_ONE_LAUNCH; additive since, same number:
+                              mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -595,6 +600,96 @@ int mpx_encode_replies_reserve(mpx_engine* eng, size_t max_n);
 int mpx_encode_replies_dev(mpx_engine* eng, const mpx_reply_rec* d_recs, size_t n,
                            uint32_t n_clients, uint8_t ok, int32_t leader, uint8_t* d_out,
                            uint64_t* d_client_off, void* stream);
+
+/* ---- the acceptor side: batched handleAccept and its AcceptReply bytes ---------------------
+ * A replica answers the Accepts of every group it does not lead. mpx_accept_handle applies
+ *   bareminpaxos.(*Replica).handleAccept  src/bareminpaxos/bareminpaxos.go:753-806  (MIN)
+ *   paxos.(*Replica).handleAccept         src/paxos/paxos.go:470-520               (CLASSIC)
+ * to a batch of Accept headers; what it emits is what mpx_accept_tally consumes on the leader. */
+
+/* Accept header: minpaxosproto.Accept{LeaderId,Instance,Ballot,LastCommitted,Command,CatchUpLog}
+ * minpaxosproto.go:66-73 / paxosproto.Accept{LeaderId,Instance,Ballot,Command} paxosproto.go:30-35.
+ * Command -> value_id (a handle the host resolves). LastCommitted and CatchUpLog are read only by
+ * commented-out code in handleAccept (:767-784), so they stay on the host. */
+typedef struct mpx_accept_msg {
+    int32_t instance;
+    int32_t ballot;
+    int32_t leader_id;
+    uint32_t value_id;
+} mpx_accept_msg; /* 16 B */
+
+/* acceptor view of instanceSpace[i]: status MPX_STATUS_NIL = nil. flags: MPX_PF_HAS_PROPOSALS in,
+ * MPX_PF_REQUEUED out (same bits as mpx_prep_state.flags); the caller clears MPX_PF_REQUEUED
+ * once it has pushed the proposals back */
+typedef struct mpx_acceptor_state {
+    int32_t status;
+    int32_t ballot;
+    uint32_t value_id;
+    uint32_t flags;
+} mpx_acceptor_state; /* 16 B */
+
+/* per group: r.defaultBallot (read only: handleAccept never writes it) and r.Id */
+typedef struct mpx_acceptor_group {
+    int32_t default_ballot;
+    int32_t self_id;
+} mpx_acceptor_group; /* 8 B */
+
+#define MPX_AH_REPLIED 1u /* replyAccept was called: replies[i] / reply_to[i] are valid         */
+#define MPX_AH_STORED 2u  /* instance installed or updated: the host stores Command and does
+                             recordInstanceMetadata + recordCommands + sync (MIN :793-800,
+                             CLASSIC :513-517)                                                  */
+#define MPX_AH_REQUEUE 4u /* CLASSIC :495-502: clientProposals were pushed back on ProposeChan  */
+
+/* msgs[n] under the contract above (grouped by instance, ascending; slot order = arrival order).
+ * Window index idx = instance - inst_base belongs to group idx / ipg; n_inst == n_groups * ipg
+ * (a single log: n_groups = 1, ipg = n_inst). st[n_inst] is updated in place; a nil instance is
+ * legal input (the acceptor creates it). Outputs are slot-aligned with msgs, one entry per
+ * message, always written: effect[i] (MPX_AH_*); where REPLIED, replies[i] (id = the group's
+ * self_id in MIN, -1 in CLASSIC, whose wire has no Id) and reply_to[i] = msgs[i].leader_id;
+ * elsewhere an all-zero record and reply_to[i] = -1.
+ *   MIN: an Accept for an instance that is ACCEPTED at the message's ballot is ignored; otherwise,
+ *   if the ballot equals default_ballot, the instance becomes {ACCEPTED, ballot, value_id, flags 0}
+ *   (whatever its status was) and the reply is {instance, OK, ballot, self_id}; otherwise nothing.
+ *   CLASSIC: every message replies. nil: ballot < default_ballot -> {FALSE, default_ballot}, else
+ *   install {ACCEPTED, ballot, value_id, 0} and reply {TRUE, default_ballot}; inst.ballot > ballot
+ *   -> {FALSE, inst.ballot}; inst.ballot < ballot -> take value and ballot, ACCEPTED, {TRUE, ballot},
+ *   proposals requeued (MPX_PF_HAS_PROPOSALS -> MPX_PF_REQUEUED, MPX_AH_REQUEUE); equal -> take the
+ *   value, ACCEPTED unless COMMITTED, {TRUE, default_ballot}. OK implies MPX_AH_STORED.
+ * Errors: an instance outside the window (the reference's instanceSpace index panics) ->
+ * MPX_E_NIL_INSTANCE; leader_id outside [0, N) on a message that replies (SendMsg indexes
+ * PeerWriters, genericsmr.go:501) -> MPX_E_BAD_ID; order -> MPX_E_INVAL.                        */
+int mpx_accept_handle(mpx_engine* eng, const mpx_accept_msg* msgs, size_t n,
+                      mpx_acceptor_state* st, size_t n_inst, int32_t inst_base,
+                      const mpx_acceptor_group* groups, size_t n_groups, uint32_t ipg,
+                      mpx_accept_reply* replies, int32_t* reply_to, uint8_t* effect);
+/* device form: d_st_in / d_st_out may alias; d_st_out[i] is written only for instances that have
+ * messages. One kernel, no scratch, no control words.                                          */
+int mpx_accept_handle_dev(mpx_engine* eng, const mpx_accept_msg* d_msgs, size_t n,
+                          const mpx_acceptor_state* d_st_in, mpx_acceptor_state* d_st_out,
+                          size_t n_inst, int32_t inst_base, const mpx_acceptor_group* d_groups,
+                          size_t n_groups, uint32_t ipg, mpx_accept_reply* d_replies,
+                          int32_t* d_reply_to, uint8_t* d_effect, void* stream);
+
+/* The frames replyAccept -> SendMsg (genericsmr.go:499-512) writes: the code byte
+ * MPX_PEER_ACCEPT_REPLY, then AcceptReply.Marshal, little endian:
+ *   MIN      14 B  [13][Instance i32][OK u8][Ballot i32][Id i32]  (minpaxosprotomarsh.go:545-566)
+ *   CLASSIC  10 B  [13][Instance i32][OK u8][Ballot i32]          (paxosprotomarsh.go:306-322)
+ * by mpx_config.mode. replies[i] goes to destination reply_to[i] (< 0: skipped; >= n_dest: the
+ * call fails with MPX_E_INVAL); n_dest <= MPX_MAX_REPLICAS. out (frame bytes x n) receives,
+ * destination by destination, each destination's frames in array order, back to back;
+ * destination d's run is out[dest_off[d] .. dest_off[d+1]) (dest_off: n_dest+1 entries).       */
+#define MPX_ACCEPT_REPLY_FRAME_MIN 14
+#define MPX_ACCEPT_REPLY_FRAME_CLASSIC 10
+int mpx_encode_accept_replies(mpx_engine* eng, const mpx_accept_reply* replies,
+                              const int32_t* reply_to, size_t n, uint32_t n_dest, uint8_t* out,
+                              uint64_t* dest_off);
+/* scratch for _dev calls of up to max_n replies (grows only; the dev entry never allocates). The
+ * scratch lives in the handle: like the other *_dev calls that keep scratch there, encodes of one
+ * handle run in one stream order, and a larger reserve invalidates graphs captured before it.   */
+int mpx_encode_accept_replies_reserve(mpx_engine* eng, size_t max_n);
+int mpx_encode_accept_replies_dev(mpx_engine* eng, const mpx_accept_reply* d_replies,
+                                  const int32_t* d_reply_to, size_t n, uint32_t n_dest,
+                                  uint8_t* d_out, uint64_t* d_dest_off, void* stream);
 
 /* ---- instance-log encoding ----------------------------------
  * A run of log records (instance metadata + commands [cmd_off[i], cmd_off[i+1]) of the SoA

@@ -87,6 +87,11 @@ struct mpx_engine {
     // durable-log replay staging: log bytes, records, op, key, val, last_rec, scalars
     DevBuf rp[7];
     DevBuf replay_work;  // the binned slot maximum (mpx_replay_durable_reserve)
+    // acceptor step staging: messages, states, groups, replies, reply_to, effect
+    DevBuf ah[6];
+    // AcceptReply encoding: staging (replies, reply_to, bytes, offsets) + scratch
+    DevBuf are[4];
+    DevBuf are_work;
     mpx::ApplyOpts apply{};  // mpx_config.apply_* (fixed for the handle's life)
     // replica-sized mpx_apply calls: pinned, GPU-mapped staging the one-launch kernel reads the
     // commands from and writes the results to (no DMA copies on the call's path)
@@ -384,6 +389,11 @@ int mpx_close(mpx_engine* e) {
     for (auto& x : e->rp)
         if (x.p) (void)hipFree(x.p);
     if (e->replay_work.p) (void)hipFree(e->replay_work.p);
+    for (auto& x : e->ah)
+        if (x.p) (void)hipFree(x.p);
+    for (auto& x : e->are)
+        if (x.p) (void)hipFree(x.p);
+    if (e->are_work.p) (void)hipFree(e->are_work.p);
     if (e->worklist.p) (void)hipFree(e->worklist.p);
     if (e->d_wcount) (void)hipFree(e->d_wcount);
     if (e->kv_ready) free_kv(e->kv);
@@ -1207,6 +1217,134 @@ int mpx_encode_replies(mpx_engine* e, const mpx_reply_rec* recs, size_t n, uint3
     int rc = finish(e);
     if (rc == MPX_E_INVAL) return fail(e, MPX_E_INVAL, "a reply names a client >= n_clients");
     return rc;
+}
+
+// ---- the acceptor side: handleAccept and the AcceptReply bytes ------------------------------
+int mpx_accept_handle_dev(mpx_engine* e, const mpx_accept_msg* d_msgs, size_t n,
+                          const mpx_acceptor_state* d_st_in, mpx_acceptor_state* d_st_out,
+                          size_t n_inst, int32_t inst_base, const mpx_acceptor_group* d_groups,
+                          size_t n_groups, uint32_t ipg, mpx_accept_reply* d_replies,
+                          int32_t* d_reply_to, uint8_t* d_effect, void* stream) {
+    if (!e) return MPX_E_INVAL;
+    if (!mpx::launch_accept_handle)
+        return fail(e, MPX_E_UNSUPPORTED, "mpx_accept_handle: the acceptor kernels are not built in");
+    if ((n && (!d_msgs || !d_replies || !d_reply_to || !d_effect)) ||
+        (n_inst && (!d_st_in || !d_st_out)) || !d_groups)
+        return fail(e, MPX_E_INVAL, "null argument");
+    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
+        n_inst > (1ull << 32))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    if (n >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "more than 2^32-2 records");
+    HIPCHK(e, mpx::launch_accept_handle(e->cfg.mode, d_msgs, n, d_st_in, d_st_out, n_inst,
+                                        inst_base, d_groups, n_groups, ipg, e->cfg.n_replicas,
+                                        d_replies, d_reply_to, d_effect, e->d_err,
+                                        pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_accept_handle(mpx_engine* e, const mpx_accept_msg* msgs, size_t n, mpx_acceptor_state* st,
+                      size_t n_inst, int32_t inst_base, const mpx_acceptor_group* groups,
+                      size_t n_groups, uint32_t ipg, mpx_accept_reply* replies, int32_t* reply_to,
+                      uint8_t* effect) {
+    if (!e) return MPX_E_INVAL;
+    if (!mpx::launch_accept_handle)
+        return fail(e, MPX_E_UNSUPPORTED, "mpx_accept_handle: the acceptor kernels are not built in");
+    if ((n && (!msgs || !replies || !reply_to || !effect)) || (n_inst && !st) || !groups)
+        return fail(e, MPX_E_INVAL, "null argument");
+    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
+        n_inst > (1ull << 32))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    CK(begin(e));
+    GROW(e, e->ah[0], n * sizeof(mpx_accept_msg));
+    GROW(e, e->ah[1], n_inst * sizeof(mpx_acceptor_state));
+    GROW(e, e->ah[2], n_groups * sizeof(mpx_acceptor_group));
+    GROW(e, e->ah[3], n * sizeof(mpx_accept_reply));
+    GROW(e, e->ah[4], n * sizeof(int32_t));
+    GROW(e, e->ah[5], n);
+    CK(h2d(e, e->ah[0].p, msgs, n * sizeof(mpx_accept_msg)));
+    CK(h2d(e, e->ah[1].p, st, n_inst * sizeof(mpx_acceptor_state)));
+    CK(h2d(e, e->ah[2].p, groups, n_groups * sizeof(mpx_acceptor_group)));
+    CK(mpx_accept_handle_dev(e, (const mpx_accept_msg*)e->ah[0].p, n,
+                             (const mpx_acceptor_state*)e->ah[1].p,
+                             (mpx_acceptor_state*)e->ah[1].p, n_inst, inst_base,
+                             (const mpx_acceptor_group*)e->ah[2].p, n_groups, ipg,
+                             (mpx_accept_reply*)e->ah[3].p, (int32_t*)e->ah[4].p,
+                             (uint8_t*)e->ah[5].p, e->stream));
+    CK(d2h(e, st, e->ah[1].p, n_inst * sizeof(mpx_acceptor_state)));
+    CK(d2h(e, replies, e->ah[3].p, n * sizeof(mpx_accept_reply)));
+    CK(d2h(e, reply_to, e->ah[4].p, n * sizeof(int32_t)));
+    CK(d2h(e, effect, e->ah[5].p, n));
+    return finish(e);
+}
+
+static size_t accept_reply_frame(const mpx_engine* e) {
+    return e->cfg.mode == MPX_MODE_MIN ? MPX_ACCEPT_REPLY_FRAME_MIN : MPX_ACCEPT_REPLY_FRAME_CLASSIC;
+}
+
+int mpx_encode_accept_replies_reserve(mpx_engine* e, size_t max_n) {
+    if (!e) return MPX_E_INVAL;
+    if (!mpx::accept_replies_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED,
+                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
+    if (max_n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    CK(begin(e));
+    GROW(e, e->are_work, mpx::accept_replies_work_bytes(max_n));
+    return finish(e);
+}
+
+int mpx_encode_accept_replies_dev(mpx_engine* e, const mpx_accept_reply* d_replies,
+                                  const int32_t* d_reply_to, size_t n, uint32_t n_dest,
+                                  uint8_t* d_out, uint64_t* d_dest_off, void* stream) {
+    if (!e) return MPX_E_INVAL;
+    if (!mpx::launch_encode_accept_replies || !mpx::accept_replies_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED,
+                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
+    if (!n_dest || n_dest > MPX_MAX_REPLICAS || !d_dest_off ||
+        (n && (!d_replies || !d_reply_to || !d_out)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    if (n && e->are_work.cap < mpx::accept_replies_work_bytes(n))
+        return fail(e, MPX_E_INVAL,
+                    "mpx_encode_accept_replies_dev: call mpx_encode_accept_replies_reserve(n) "
+                    "first (the dev entry point never allocates)");
+    HIPCHK(e, mpx::launch_encode_accept_replies(e->cfg.mode, d_replies, d_reply_to, n, n_dest,
+                                                d_out, d_dest_off, e->are_work.p,
+                                                e->are_work.cap, e->d_err, pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
+                              const int32_t* reply_to, size_t n, uint32_t n_dest, uint8_t* out,
+                              uint64_t* dest_off) {
+    if (!e) return MPX_E_INVAL;
+    if (!mpx::launch_encode_accept_replies || !mpx::accept_replies_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED,
+                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
+    if (!n_dest || n_dest > MPX_MAX_REPLICAS || !dest_off || (n && (!replies || !reply_to || !out)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    const size_t frame = accept_reply_frame(e);
+    CK(begin(e));
+    GROW(e, e->are[0], n * sizeof(mpx_accept_reply));
+    GROW(e, e->are[1], n * sizeof(int32_t));
+    GROW(e, e->are[2], n * frame);
+    GROW(e, e->are[3], ((size_t)n_dest + 1) * sizeof(uint64_t));
+    if (n) GROW(e, e->are_work, mpx::accept_replies_work_bytes(n));
+    CK(h2d(e, e->are[0].p, replies, n * sizeof(mpx_accept_reply)));
+    CK(h2d(e, e->are[1].p, reply_to, n * sizeof(int32_t)));
+    CK(mpx_encode_accept_replies_dev(e, (const mpx_accept_reply*)e->are[0].p,
+                                     (const int32_t*)e->are[1].p, n, n_dest,
+                                     (uint8_t*)e->are[2].p, (uint64_t*)e->are[3].p, e->stream));
+    CK(d2h(e, dest_off, e->are[3].p, ((size_t)n_dest + 1) * sizeof(uint64_t)));
+    const int rc = finish(e);
+    if (rc == MPX_E_INVAL) return fail(e, MPX_E_INVAL, "a reply names a destination >= n_dest");
+    if (rc) return rc;
+    // the frames written: skipped slots leave the rest of out untouched
+    const uint64_t total = dest_off[n_dest];
+    if (total > n * frame) return fail(e, MPX_E_HIP, "mpx_encode_accept_replies: bad offsets");
+    CK(d2h(e, out, e->are[2].p, total));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MPX_OK;
 }
 
 // ---- §8(f) ranks 3/4: instance-log encoding -------------------------------------------------

@@ -10,6 +10,8 @@ Names and argument meaning follow the reference handlers they replace:
   group_step          <- handleAcceptReply + executeCommands for many replicas at once
   decode_peer_stream  <- genericsmr.replicaListener framing + AcceptReply.Unmarshal
   encode_replies      <- the ProposeReplyTS fan-out (ReplyProposeTS per executed command)
+  accept_handle       <- bareminpaxos / paxos  handleAccept (the acceptor's half of Phase 2)
+  encode_accept_replies <- replyAccept -> SendMsg: the AcceptReply frames per leader connection
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -392,6 +394,58 @@ class Engine:
         self._check(self.lib.mpx_encode_replies_dev(self.h, d_recs, n, n_clients, ok, leader,
                                                     d_out, d_off, stream),
                     "mpx_encode_replies_dev")
+
+    # ---- the acceptor side: handleAccept and the AcceptReply bytes ----------------------------
+    def accept_handle(self, msgs, st, groups, inst_base=0, ipg=None):
+        """msgs: ACCEPT_MSG grouped by instance, ascending; st: ACCEPTOR_STATE of the window
+        (copied); groups: ACCEPTOR_GROUP, group g owning window indices [g*ipg, (g+1)*ipg)
+        (ipg defaults to the whole window: one log). Returns (st, replies ACCEPT_REPLY[n],
+        reply_to int32[n], effect uint8[n]), the last three slot-aligned with msgs."""
+        msgs = _c(msgs, R.ACCEPT_MSG)
+        st = np.array(st, dtype=R.ACCEPTOR_STATE, copy=True)
+        groups = _c(np.atleast_1d(groups), R.ACCEPTOR_GROUP)
+        n = len(msgs)
+        ipg = (len(st) // len(groups) if len(groups) else 0) if ipg is None else ipg
+        rep = np.zeros(max(n, 1), R.ACCEPT_REPLY)
+        to = np.zeros(max(n, 1), np.int32)
+        eff = np.zeros(max(n, 1), np.uint8)
+        rc = self.lib.mpx_accept_handle(self.h, _ptr(msgs), n, _ptr(st), len(st), inst_base,
+                                        _ptr(groups), len(groups), ipg, _ptr(rep), _ptr(to),
+                                        _ptr(eff))
+        self._check(rc, "mpx_accept_handle")
+        return st, rep[:n], to[:n], eff[:n]
+
+    def accept_handle_dev(self, d_msgs, n, d_st_in, d_st_out, n_inst, inst_base, d_groups,
+                          n_groups, ipg, d_replies, d_reply_to, d_effect, stream=None):
+        rc = self.lib.mpx_accept_handle_dev(self.h, d_msgs, n, d_st_in, d_st_out, n_inst,
+                                            inst_base, d_groups, n_groups, ipg, d_replies,
+                                            d_reply_to, d_effect, stream)
+        self._check(rc, "mpx_accept_handle_dev")
+
+    def encode_accept_replies(self, replies, reply_to, n_dest=None):
+        """replies: ACCEPT_REPLY, reply_to: int32 destination per reply (< 0: skipped). Returns
+        (bytes uint8, dest_off u64[n_dest+1]): destination d's connection receives
+        out[dest_off[d]:dest_off[d+1]], its AcceptReply frames in array order."""
+        replies = _c(replies, R.ACCEPT_REPLY)
+        reply_to = _c(reply_to, np.int32)
+        n = len(replies)
+        n_dest = self.n_replicas if n_dest is None else n_dest
+        out = np.zeros(max(n * R.ACCEPT_REPLY_FRAME[self.mode], 1), np.uint8)
+        off = np.zeros(n_dest + 1, np.uint64)
+        self._check(self.lib.mpx_encode_accept_replies(self.h, _ptr(replies), _ptr(reply_to), n,
+                                                       n_dest, _ptr(out), _ptr(off)),
+                    "mpx_encode_accept_replies")
+        return out[:int(off[-1])], off
+
+    def encode_accept_replies_reserve(self, max_n):
+        self._check(self.lib.mpx_encode_accept_replies_reserve(self.h, max_n),
+                    "mpx_encode_accept_replies_reserve")
+
+    def encode_accept_replies_dev(self, d_replies, d_reply_to, n, n_dest, d_out, d_off,
+                                  stream=None):
+        self._check(self.lib.mpx_encode_accept_replies_dev(self.h, d_replies, d_reply_to, n,
+                                                           n_dest, d_out, d_off, stream),
+                    "mpx_encode_accept_replies_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

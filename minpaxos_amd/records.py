@@ -88,6 +88,23 @@ LOG_CATCHUP, LOG_DURABLE = 0, 1
 DURABLE_REC_BYTES = 29
 LOG_REC = np.dtype([("ballot", "<i4"), ("status", "<i4"), ("inst_no", "<i4"), ("pad", "<u4")])
 
+# the acceptor side (mpx_accept_handle / mpx_encode_accept_replies)
+# mpx_accept_msg  <- minpaxosproto.Accept / paxosproto.Accept header (Command -> value_id)
+ACCEPT_MSG = np.dtype([("instance", "<i4"), ("ballot", "<i4"), ("leader_id", "<i4"),
+                       ("value_id", "<u4")])
+# mpx_acceptor_state  <- the acceptor's view of instanceSpace[i] (flags: PF_HAS_PROPOSALS in,
+# PF_REQUEUED out)
+ACCEPTOR_STATE = np.dtype([("status", "<i4"), ("ballot", "<i4"), ("value_id", "<u4"),
+                           ("flags", "<u4")])
+# mpx_acceptor_group  <- r.defaultBallot, r.Id
+ACCEPTOR_GROUP = np.dtype([("default_ballot", "<i4"), ("self_id", "<i4")])
+# effect[i] of mpx_accept_handle
+AH_REPLIED, AH_STORED, AH_REQUEUE = 1, 2, 4
+# frame bytes of one AcceptReply on a peer connection (code byte + Marshal), by mode
+ACCEPT_REPLY_FRAME = {MODE_MIN: 14, MODE_CLASSIC: 10}
+
+assert ACCEPT_MSG.itemsize == 16 and ACCEPTOR_STATE.itemsize == 16
+assert ACCEPTOR_GROUP.itemsize == 8
 assert LOG_REC.itemsize == 16
 assert REPLY_REC.itemsize == 24
 assert PEER_FRAME.itemsize == 8 and DECODE_RESULT.itemsize == 32
