@@ -1,8 +1,9 @@
 // engine.cpp — the C ABI (include/mpx.h) over the gfx950 kernels.
 //
-// Host-pointer entry points stage through engine-owned device buffers on the engine's HIP
-// stream and return when results are back in caller memory. *_dev entry points enqueue on the
-// caller's stream with device pointers, never allocate and never synchronise.
+// *_dev entry points enqueue on the caller's stream with device pointers, never allocate and never
+// synchronise. A host-pointer entry point is a staging wrapper over its _dev form: host-only
+// checks, begin, lay the call out in the engine's staging arena (Stage) and copy in, the _dev form
+// on the engine's stream, copy out, finish; it returns when results are back in caller memory.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 
@@ -65,33 +67,14 @@ struct mpx_engine {
     uint32_t* d_err = nullptr;
     unsigned long long* d_red = nullptr;
     uint32_t* d_tctl = nullptr;  // tile kernels' control words (kTileCtlWords, zero between calls)
-    // host-API staging
-    DevBuf b[12];
+    // host-API staging: one arena, laid out afresh by every host-pointer call (Stage); it grows
+    // to the largest single call
+    DevBuf arena;
     // global KV table (mpx_apply)
     mpx::KvTable kv{};
     bool kv_ready = false;
-    DevBuf apply_work;
-    // peer stream decode: staging (bytes, AcceptReplies, other frames, result) + scratch
-    DevBuf dec[4];
-    DevBuf decode_work;
-    // full stream decode: staging (bytes, AcceptReplies, PrepareReplies, var frames, other,
-    // result) + scratch
-    DevBuf sd[6];
-    DevBuf stream_work;
-    // client reply fan-out: staging (records, bytes, offsets) + scratch
-    DevBuf fan[3];
-    DevBuf fan_work;
-    // instance-log encoding: staging (records, offsets, op, key, val, out, rec_off) + scratch
-    DevBuf lg[7];
-    DevBuf log_work;
-    // durable-log replay staging: log bytes, records, op, key, val, last_rec, scalars
-    DevBuf rp[7];
-    DevBuf replay_work;  // the binned slot maximum (mpx_replay_durable_reserve)
-    // acceptor step staging: messages, states, groups, replies, reply_to, effect
-    DevBuf ah[6];
-    // AcceptReply encoding: staging (replies, reply_to, bytes, offsets) + scratch
-    DevBuf are[4];
-    DevBuf are_work;
+    // the families' scratch: grown by the host forms and the *_reserve calls, never by a _dev form
+    DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work;
     mpx::ApplyOpts apply{};  // mpx_config.apply_* (fixed for the handle's life)
     // replica-sized mpx_apply calls: pinned, GPU-mapped staging the one-launch kernel reads the
     // commands from and writes the results to (no DMA copies on the call's path)
@@ -191,6 +174,74 @@ int d2h(mpx_engine* e, void* h, const void* d, size_t bytes) {
         int _c = (x);          \
         if (_c) return _c;     \
     } while (0)
+
+// One host-pointer call's layout of the staging arena. add() names the call's slots at
+// 256-byte-aligned offsets (so every slot keeps the 16-byte alignment the tile kernels' vector
+// loads need); commit() grows the arena once, to the sum; in() / out() / at() resolve a slot
+// against the grown arena, so they are valid only after commit() and no pointer survives a grow.
+// An optional array the caller did not pass gets a 0-byte slot and at(slot, nullptr) == nullptr.
+struct Slot {
+    size_t off, bytes;
+};
+class Stage {
+  public:
+    explicit Stage(mpx_engine* e) : e_(e) {}
+    Slot add(size_t bytes) {
+        const Slot s{end_, bytes};
+        end_ += (bytes + 255) & ~(size_t)255;
+        return s;
+    }
+    int commit() {
+        CK(grow(e_, e_->arena, std::max(end_, (size_t)1)));  // (never a null base)
+        base_ = (char*)e_->arena.p;
+        return MPX_OK;
+    }
+    template <typename T>
+    T* at(Slot s) const {
+        return reinterpret_cast<T*>(base_ + s.off);
+    }
+    template <typename T>
+    T* at(Slot s, const void* asked) const {
+        return asked ? at<T>(s) : nullptr;
+    }
+    int in(Slot s, const void* h) const { return h2d(e_, base_ + s.off, h, s.bytes); }
+    int out(Slot s, void* h) const { return d2h(e_, h, base_ + s.off, s.bytes); }
+    int out(Slot s, void* h, size_t bytes) const { return d2h(e_, h, base_ + s.off, bytes); }
+
+  private:
+    mpx_engine* e_;
+    size_t end_ = 0;
+    char* base_ = nullptr;
+};
+
+// the body of every *_reserve call: grow a family's scratch so its _dev form can run
+int reserve(mpx_engine* e, DevBuf& work, uint64_t bytes) {
+    CK(begin(e));
+    GROW(e, work, bytes);
+    return finish(e);
+}
+// ... and the _dev form's side of it: the scratch must already hold `need` bytes
+int reserved(mpx_engine* e, const DevBuf& work, uint64_t need, const char* entry,
+             const char* reserve_call) {
+    if (work.cap >= need) return MPX_OK;
+    return fail(e, MPX_E_INVAL, std::string(entry) + ": call " + reserve_call +
+                                    " first (the dev entry point never allocates)");
+}
+
+// size limits the host and _dev forms of a family share
+int record_limit(mpx_engine* e, size_t n) {
+    if (n >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "more than 2^32-2 records");
+    return MPX_OK;
+}
+int reply_limit(mpx_engine* e, size_t n) {
+    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    return MPX_OK;
+}
+int decode_limit(mpx_engine* e, size_t len) {
+    if (len > MPX_DECODE_MAX_BYTES)
+        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
+    return MPX_OK;
+}
 
 void free_kv(mpx::KvTable& t) {
     if (t.keys) (void)hipFree(t.keys);
@@ -369,32 +420,11 @@ int mpx_close(mpx_engine* e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->comm) ncclCommDestroy(e->comm);
-    for (auto& x : e->b)
-        if (x.p) (void)hipFree(x.p);
-    if (e->apply_work.p) (void)hipFree(e->apply_work.p);
+    for (DevBuf* x : {&e->arena, &e->apply_work, &e->decode_work, &e->stream_work, &e->fan_work,
+                      &e->log_work, &e->replay_work, &e->are_work, &e->worklist})
+        if (x->p) (void)hipFree(x->p);
     if (e->pin_io.p) (void)hipHostFree(e->pin_io.p);
     if (e->pin_staged.p) (void)hipHostFree(e->pin_staged.p);
-    for (auto& x : e->dec)
-        if (x.p) (void)hipFree(x.p);
-    if (e->decode_work.p) (void)hipFree(e->decode_work.p);
-    for (auto& x : e->sd)
-        if (x.p) (void)hipFree(x.p);
-    if (e->stream_work.p) (void)hipFree(e->stream_work.p);
-    for (auto& x : e->fan)
-        if (x.p) (void)hipFree(x.p);
-    if (e->fan_work.p) (void)hipFree(e->fan_work.p);
-    for (auto& x : e->lg)
-        if (x.p) (void)hipFree(x.p);
-    if (e->log_work.p) (void)hipFree(e->log_work.p);
-    for (auto& x : e->rp)
-        if (x.p) (void)hipFree(x.p);
-    if (e->replay_work.p) (void)hipFree(e->replay_work.p);
-    for (auto& x : e->ah)
-        if (x.p) (void)hipFree(x.p);
-    for (auto& x : e->are)
-        if (x.p) (void)hipFree(x.p);
-    if (e->are_work.p) (void)hipFree(e->are_work.p);
-    if (e->worklist.p) (void)hipFree(e->worklist.p);
     if (e->d_wcount) (void)hipFree(e->d_wcount);
     if (e->kv_ready) free_kv(e->kv);
     if (e->d_err) (void)hipFree(e->d_err);
@@ -423,28 +453,26 @@ int mpx_accept_tally(mpx_engine* e, const mpx_accept_reply* recs, size_t n, mpx_
     if (!e) return MPX_E_INVAL;
     if ((n && !recs) || (n_inst && !st) || !committed_upto || !peer_commits)
         return fail(e, MPX_E_INVAL, "null argument");
-    if (n >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "more than 2^32-2 records");
+    CK(record_limit(e, n));
     const int N = e->cfg.n_replicas;
-    CK(begin(e));
-    GROW(e, e->b[0], n * sizeof(mpx_accept_reply));
-    GROW(e, e->b[1], n_inst * sizeof(mpx_inst_state));
-    GROW(e, e->b[2], n_inst);
-    GROW(e, e->b[3], (1 + N) * sizeof(int32_t));
     int32_t sc[1 + MPX_MAX_REPLICAS];
     sc[0] = *committed_upto;
     memcpy(sc + 1, peer_commits, N * sizeof(int32_t));
-    CK(h2d(e, e->b[0].p, recs, n * sizeof(mpx_accept_reply)));
-    CK(h2d(e, e->b[1].p, st, n_inst * sizeof(mpx_inst_state)));
-    CK(h2d(e, e->b[3].p, sc, (1 + N) * sizeof(int32_t)));
-    uint8_t* d_dec = decided_out ? (uint8_t*)e->b[2].p : nullptr;
-    HIPCHK(e, mpx::launch_accept_tally(e->cfg.mode, (const mpx_accept_reply*)e->b[0].p, n,
-                                       (const mpx_inst_state*)e->b[1].p,
-                                       (mpx_inst_state*)e->b[1].p, n_inst, inst_base, N,
-                                       (int32_t*)e->b[3].p, d_dec, e->d_red, e->d_tctl,
-                                       e->d_err, e->stream));
-    CK(d2h(e, st, e->b[1].p, n_inst * sizeof(mpx_inst_state)));
-    CK(d2h(e, sc, e->b[3].p, (1 + N) * sizeof(int32_t)));
-    if (decided_out) CK(d2h(e, decided_out, d_dec, n_inst));
+    CK(begin(e));
+    Stage L(e);
+    const Slot s_rec = L.add(n * sizeof(mpx_accept_reply)),
+               s_st = L.add(n_inst * sizeof(mpx_inst_state)),
+               s_sc = L.add((1 + N) * sizeof(int32_t)), s_dec = L.add(decided_out ? n_inst : 0);
+    CK(L.commit());
+    CK(L.in(s_rec, recs));
+    CK(L.in(s_st, st));
+    CK(L.in(s_sc, sc));
+    mpx_inst_state* d_st = L.at<mpx_inst_state>(s_st);
+    CK(mpx_accept_tally_dev(e, L.at<mpx_accept_reply>(s_rec), n, d_st, d_st, n_inst, inst_base,
+                            L.at<int32_t>(s_sc), L.at<uint8_t>(s_dec, decided_out), e->stream));
+    CK(L.out(s_st, st));
+    CK(L.out(s_sc, sc));
+    CK(L.out(s_dec, decided_out));
     CK(finish(e));
     *committed_upto = sc[0];
     memcpy(peer_commits, sc + 1, N * sizeof(int32_t));
@@ -458,7 +486,7 @@ int mpx_accept_tally_dev(mpx_engine* e, const mpx_accept_reply* d_recs, size_t n
     if (!e) return MPX_E_INVAL;
     if ((n && !d_recs) || (n_inst && (!d_st_in || !d_st_out)) || !d_scalars)
         return fail(e, MPX_E_INVAL, "null argument");
-    if (n >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "more than 2^32-2 records");
+    CK(record_limit(e, n));
     HIPCHK(e, mpx::launch_accept_tally(e->cfg.mode, d_recs, n, d_st_in, d_st_out, n_inst,
                                        inst_base, e->cfg.n_replicas, d_scalars, d_decided,
                                        e->d_red, e->d_tctl, e->d_err, pick(e, stream)));
@@ -470,13 +498,14 @@ int mpx_committed_prefix(mpx_engine* e, const mpx_inst_state* st, size_t n_inst,
     if (!e) return MPX_E_INVAL;
     if ((n_inst && !st) || !committed_upto) return fail(e, MPX_E_INVAL, "null argument");
     CK(begin(e));
-    GROW(e, e->b[1], n_inst * sizeof(mpx_inst_state));
-    GROW(e, e->b[3], sizeof(int32_t));
-    CK(h2d(e, e->b[1].p, st, n_inst * sizeof(mpx_inst_state)));
-    CK(h2d(e, e->b[3].p, committed_upto, sizeof(int32_t)));
-    HIPCHK(e, mpx::launch_committed_prefix((const mpx_inst_state*)e->b[1].p, n_inst, inst_base,
-                                           (int32_t*)e->b[3].p, e->d_red, e->stream));
-    CK(d2h(e, committed_upto, e->b[3].p, sizeof(int32_t)));
+    Stage L(e);
+    const Slot s_st = L.add(n_inst * sizeof(mpx_inst_state)), s_cu = L.add(sizeof(int32_t));
+    CK(L.commit());
+    CK(L.in(s_st, st));
+    CK(L.in(s_cu, committed_upto));
+    HIPCHK(e, mpx::launch_committed_prefix(L.at<mpx_inst_state>(s_st), n_inst, inst_base,
+                                           L.at<int32_t>(s_cu), e->d_red, e->stream));
+    CK(L.out(s_cu, committed_upto));
     return finish(e);
 }
 
@@ -488,22 +517,21 @@ int mpx_prepare_select(mpx_engine* e, const mpx_prepare_reply* recs, size_t n, m
     if ((n && !recs) || (n_inst && !st) || !default_ballot)
         return fail(e, MPX_E_INVAL, "null argument");
     CK(begin(e));
-    GROW(e, e->b[0], n * sizeof(mpx_prepare_reply));
-    GROW(e, e->b[1], n_inst * sizeof(mpx_prep_state));
-    GROW(e, e->b[2], n_inst);
-    GROW(e, e->b[3], sizeof(int32_t));
-    CK(h2d(e, e->b[0].p, recs, n * sizeof(mpx_prepare_reply)));
-    CK(h2d(e, e->b[1].p, st, n_inst * sizeof(mpx_prep_state)));
-    CK(h2d(e, e->b[3].p, default_ballot, sizeof(int32_t)));
-    uint8_t* d_prep = prepared_out ? (uint8_t*)e->b[2].p : nullptr;
-    HIPCHK(e, mpx::launch_prepare_classic((const mpx_prepare_reply*)e->b[0].p, n,
-                                          (const mpx_prep_state*)e->b[1].p,
-                                          (mpx_prep_state*)e->b[1].p, n_inst, inst_base,
-                                          e->cfg.n_replicas, (int32_t*)e->b[3].p, d_prep,
-                                          e->d_tctl, e->d_err, e->stream));
-    CK(d2h(e, st, e->b[1].p, n_inst * sizeof(mpx_prep_state)));
-    CK(d2h(e, default_ballot, e->b[3].p, sizeof(int32_t)));
-    if (prepared_out) CK(d2h(e, prepared_out, d_prep, n_inst));
+    Stage L(e);
+    const Slot s_rec = L.add(n * sizeof(mpx_prepare_reply)),
+               s_st = L.add(n_inst * sizeof(mpx_prep_state)), s_db = L.add(sizeof(int32_t)),
+               s_prep = L.add(prepared_out ? n_inst : 0);
+    CK(L.commit());
+    CK(L.in(s_rec, recs));
+    CK(L.in(s_st, st));
+    CK(L.in(s_db, default_ballot));
+    mpx_prep_state* d_st = L.at<mpx_prep_state>(s_st);
+    CK(mpx_prepare_select_dev(e, L.at<mpx_prepare_reply>(s_rec), n, d_st, d_st, n_inst, inst_base,
+                              L.at<int32_t>(s_db), L.at<uint8_t>(s_prep, prepared_out),
+                              e->stream));
+    CK(L.out(s_st, st));
+    CK(L.out(s_db, default_ballot));
+    CK(L.out(s_prep, prepared_out));
     return finish(e);
 }
 
@@ -534,23 +562,24 @@ int mpx_prepare_select_min(mpx_engine* e, const mpx_prepare_reply_min* recs, siz
             return fail(e, MPX_E_INVAL, "grp_rec_off must be non-decreasing");
     const int N = e->cfg.n_replicas;
     CK(begin(e));
-    GROW(e, e->b[0], n * sizeof(mpx_prepare_reply_min));
-    GROW(e, e->b[4], (n_groups + 1) * sizeof(uint64_t));
-    GROW(e, e->b[1], n_groups * sizeof(mpx_group_prep_state));
-    GROW(e, e->b[5], n_groups * N * sizeof(int32_t));
-    GROW(e, e->b[6], n * sizeof(mpx_prepare_effect));
-    CK(h2d(e, e->b[0].p, recs, n * sizeof(mpx_prepare_reply_min)));
-    CK(h2d(e, e->b[4].p, grp_rec_off, (n_groups + 1) * sizeof(uint64_t)));
-    CK(h2d(e, e->b[1].p, gst, n_groups * sizeof(mpx_group_prep_state)));
-    CK(h2d(e, e->b[5].p, peer_commits, n_groups * N * sizeof(int32_t)));
-    mpx_prepare_effect* d_eff = eff ? (mpx_prepare_effect*)e->b[6].p : nullptr;
-    HIPCHK(e, mpx::launch_prepare_min((const mpx_prepare_reply_min*)e->b[0].p, n,
-                                      (const uint64_t*)e->b[4].p, (mpx_group_prep_state*)e->b[1].p,
-                                      n_groups, N, (int32_t*)e->b[5].p, d_eff, e->d_err,
-                                      e->stream));
-    CK(d2h(e, gst, e->b[1].p, n_groups * sizeof(mpx_group_prep_state)));
-    CK(d2h(e, peer_commits, e->b[5].p, n_groups * N * sizeof(int32_t)));
-    if (eff) CK(d2h(e, eff, d_eff, n * sizeof(mpx_prepare_effect)));
+    Stage L(e);
+    const Slot s_rec = L.add(n * sizeof(mpx_prepare_reply_min)),
+               s_off = L.add((n_groups + 1) * sizeof(uint64_t)),
+               s_gst = L.add(n_groups * sizeof(mpx_group_prep_state)),
+               s_pc = L.add(n_groups * N * sizeof(int32_t)),
+               s_eff = L.add(eff ? n * sizeof(mpx_prepare_effect) : 0);
+    CK(L.commit());
+    CK(L.in(s_rec, recs));
+    CK(L.in(s_off, grp_rec_off));
+    CK(L.in(s_gst, gst));
+    CK(L.in(s_pc, peer_commits));
+    CK(mpx_prepare_select_min_dev(e, L.at<mpx_prepare_reply_min>(s_rec), n, L.at<uint64_t>(s_off),
+                                  L.at<mpx_group_prep_state>(s_gst), n_groups,
+                                  L.at<int32_t>(s_pc), L.at<mpx_prepare_effect>(s_eff, eff),
+                                  e->stream));
+    CK(L.out(s_gst, gst));
+    CK(L.out(s_pc, peer_commits));
+    CK(L.out(s_eff, eff));
     return finish(e);
 }
 
@@ -592,22 +621,18 @@ int mpx_apply(mpx_engine* e, const uint8_t* op, const int64_t* key, const int64_
     }
     CK(begin(e));
     CK(ensure_kv(e));
-    GROW(e, e->b[7], m);
-    GROW(e, e->b[8], m * 8);
-    GROW(e, e->b[9], m * 8);
-    GROW(e, e->b[10], m * 8);
-    GROW(e, e->b[11], m);
     GROW(e, e->apply_work, mpx::apply_work_bytes(e->kv, e->apply, m));
-    CK(h2d(e, e->b[7].p, op, m));
-    CK(h2d(e, e->b[8].p, key, m * 8));
-    CK(h2d(e, e->b[9].p, val, m * 8));
-    mpx::ApplyWork w{e->apply_work.p, e->apply_work.cap};
-    uint8_t* d_conf = conf_prev ? (uint8_t*)e->b[11].p : nullptr;
-    HIPCHK(e, mpx::launch_apply(e->kv, (const uint8_t*)e->b[7].p, (const int64_t*)e->b[8].p,
-                                (const int64_t*)e->b[9].p, m, (int64_t*)e->b[10].p, d_conf,
-                                e->apply, w, e->d_err, e->stream));
-    CK(d2h(e, ret, e->b[10].p, m * 8));
-    if (conf_prev) CK(d2h(e, conf_prev, d_conf, m));
+    Stage L(e);
+    const Slot s_op = L.add(m), s_key = L.add(m * 8), s_val = L.add(m * 8), s_ret = L.add(m * 8),
+               s_conf = L.add(conf_prev ? m : 0);
+    CK(L.commit());
+    CK(L.in(s_op, op));
+    CK(L.in(s_key, key));
+    CK(L.in(s_val, val));
+    CK(mpx_apply_dev(e, L.at<uint8_t>(s_op), L.at<int64_t>(s_key), L.at<int64_t>(s_val), m,
+                     L.at<int64_t>(s_ret), L.at<uint8_t>(s_conf, conf_prev), e->stream));
+    CK(L.out(s_ret, ret));
+    CK(L.out(s_conf, conf_prev));
     return finish(e);
 }
 
@@ -646,10 +671,9 @@ int mpx_apply_staged(mpx_engine* e, size_t m) {
 int mpx_apply_reserve(mpx_engine* e, size_t max_cmds) {
     if (!e) return MPX_E_INVAL;
     if (max_cmds >= (1ull << 31)) return fail(e, MPX_E_UNSUPPORTED, "more than 2^31-1 commands");
-    CK(begin(e));
-    CK(ensure_kv(e));
-    GROW(e, e->apply_work, mpx::apply_reserve_bytes(e->kv, e->apply, max_cmds));
-    return finish(e);
+    HIPCHK(e, hipSetDevice(e->device));
+    CK(ensure_kv(e));  // (its size enters the scratch's)
+    return reserve(e, e->apply_work, mpx::apply_reserve_bytes(e->kv, e->apply, max_cmds));
 }
 
 int mpx_apply_dev(mpx_engine* e, const uint8_t* d_op, const int64_t* d_key, const int64_t* d_val,
@@ -657,10 +681,10 @@ int mpx_apply_dev(mpx_engine* e, const uint8_t* d_op, const int64_t* d_key, cons
     if (!e) return MPX_E_INVAL;
     if (m && (!d_op || !d_key || !d_val || !d_ret)) return fail(e, MPX_E_INVAL, "null argument");
     if (m >= (1ull << 31)) return fail(e, MPX_E_UNSUPPORTED, "more than 2^31-1 commands per call");
-    if (!e->kv_ready || e->apply_work.cap < mpx::apply_work_bytes(e->kv, e->apply, m))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_apply_dev: call mpx_apply_reserve(m) first (the dev entry point never "
-                    "allocates)");
+    // (no table yet: no scratch is enough)
+    CK(reserved(e, e->apply_work,
+                e->kv_ready ? mpx::apply_work_bytes(e->kv, e->apply, m) : UINT64_MAX,
+                "mpx_apply_dev", "mpx_apply_reserve(m)"));
     mpx::ApplyWork w{e->apply_work.p, e->apply_work.cap};
     HIPCHK(e, mpx::launch_apply(e->kv, d_op, d_key, d_val, m, d_ret, d_conf_prev,
                                 e->apply, w, e->d_err, pick(e, stream)));
@@ -688,13 +712,14 @@ int mpx_kv_export(mpx_engine* e, int64_t* keys, int64_t* vals, size_t cap, size_
     CK(d2h(e, &c, e->kv.n_present, sizeof(c)));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     const size_t want = (size_t)c;
-    GROW(e, e->b[8], std::max<size_t>(want, 1) * 8);
-    GROW(e, e->b[9], std::max<size_t>(want, 1) * 8);
-    HIPCHK(e, mpx::launch_kv_export(e->kv, (int64_t*)e->b[8].p, (int64_t*)e->b[9].p, want,
+    Stage L(e);
+    const Slot s_keys = L.add(want * 8), s_vals = L.add(want * 8);
+    CK(L.commit());
+    HIPCHK(e, mpx::launch_kv_export(e->kv, L.at<int64_t>(s_keys), L.at<int64_t>(s_vals), want,
                                     (unsigned long long*)e->d_red, e->stream));
     const size_t k = std::min(cap, want);
-    CK(d2h(e, keys, e->b[8].p, k * 8));
-    CK(d2h(e, vals, e->b[9].p, k * 8));
+    CK(L.out(s_keys, keys, k * 8));
+    CK(L.out(s_vals, vals, k * 8));
     CK(finish(e));
     *n = want;
     return MPX_OK;
@@ -705,11 +730,12 @@ int mpx_kv_import(mpx_engine* e, const int64_t* keys, const int64_t* vals, size_
     if ((n && (!keys || !vals))) return fail(e, MPX_E_INVAL, "null or invalid argument");
     CK(begin(e));
     CK(ensure_kv(e));
-    GROW(e, e->b[8], n * 8);
-    GROW(e, e->b[9], n * 8);
-    CK(h2d(e, e->b[8].p, keys, n * 8));
-    CK(h2d(e, e->b[9].p, vals, n * 8));
-    HIPCHK(e, mpx::launch_kv_import(e->kv, (const int64_t*)e->b[8].p, (const int64_t*)e->b[9].p, n,
+    Stage L(e);
+    const Slot s_keys = L.add(n * 8), s_vals = L.add(n * 8);
+    CK(L.commit());
+    CK(L.in(s_keys, keys));
+    CK(L.in(s_vals, vals));
+    HIPCHK(e, mpx::launch_kv_import(e->kv, L.at<int64_t>(s_keys), L.at<int64_t>(s_vals), n,
                                     e->d_err, e->stream));
     return finish(e);
 }
@@ -732,17 +758,16 @@ int mpx_conflict_batch(mpx_engine* e, const uint8_t* op, const int64_t* key,
     for (size_t i = 0; i < n_inst; ++i)
         if (inst_off[i + 1] < inst_off[i]) return fail(e, MPX_E_INVAL, "inst_off not sorted");
     CK(begin(e));
-    GROW(e, e->b[7], m);
-    GROW(e, e->b[8], m * 8);
-    GROW(e, e->b[4], (n_inst + 1) * 8);
-    GROW(e, e->b[11], n_inst);
-    CK(h2d(e, e->b[7].p, op, m));
-    CK(h2d(e, e->b[8].p, key, m * 8));
-    CK(h2d(e, e->b[4].p, inst_off, (n_inst + 1) * 8));
-    HIPCHK(e, mpx::launch_conflict_batch((const uint8_t*)e->b[7].p, (const int64_t*)e->b[8].p,
-                                         (const uint64_t*)e->b[4].p, n_inst,
-                                         (uint8_t*)e->b[11].p, e->stream));
-    CK(d2h(e, out, e->b[11].p, n_inst - 1));
+    Stage L(e);
+    const Slot s_op = L.add(m), s_key = L.add(m * 8), s_off = L.add((n_inst + 1) * 8),
+               s_out = L.add(n_inst - 1);
+    CK(L.commit());
+    CK(L.in(s_op, op));
+    CK(L.in(s_key, key));
+    CK(L.in(s_off, inst_off));
+    CK(mpx_conflict_batch_dev(e, L.at<uint8_t>(s_op), L.at<int64_t>(s_key), L.at<uint64_t>(s_off),
+                              n_inst, L.at<uint8_t>(s_out), e->stream));
+    CK(L.out(s_out, out));
     return finish(e);
 }
 
@@ -764,8 +789,17 @@ bool one_launch(const mpx_engine* e) { return (e->cfg.flags & MPX_FLAG_STEP_ONE_
 unsigned long long* pslots(const mpx_engine* e) {
     return one_launch(e) ? reinterpret_cast<unsigned long long*>(e->worklist.p) : nullptr;
 }
-// the device-pointer group step; d_totals (optional) gets the step totals from the same kernels
-int group_step_dev(mpx_engine* e, const mpx_group_batch* b, int64_t* d_totals, void* stream) {
+// the batch shapes the kernels take (the host form checks them before it stages anything)
+int step_shape(mpx_engine* e, const mpx_group_batch* b) {
+    if (b->ipg == 0 && b->n_groups) return fail(e, MPX_E_INVAL, "ipg must be > 0");
+    if (b->ipg > 8192) return fail(e, MPX_E_UNSUPPORTED, "more than 8192 instances per group");
+    return MPX_OK;
+}
+// the device-pointer group step; d_totals (optional) gets the step totals from the same kernels.
+// timed: record the mpx_group_step_events pair around the fast kernel (the _dev forms do, the
+// host form does not)
+int group_step_dev(mpx_engine* e, const mpx_group_batch* b, int64_t* d_totals, void* stream,
+                   bool timed = true) {
     if (!e) return MPX_E_INVAL;
     if (!b) return fail(e, MPX_E_INVAL, "null or invalid argument");
     if (b->n_groups && (!b->recs || !b->grp_rec_off || !b->st_in || !b->st_out ||
@@ -774,8 +808,7 @@ int group_step_dev(mpx_engine* e, const mpx_group_batch* b, int64_t* d_totals, v
                         !b->val || !b->cmd_off || !b->ret || !b->kv_cnt_in || !b->kv_key_in ||
                         !b->kv_val_in || !b->kv_cnt_out || !b->kv_key_out || !b->kv_val_out))
         return fail(e, MPX_E_INVAL, "null field in mpx_group_batch");
-    if (b->ipg == 0 && b->n_groups) return fail(e, MPX_E_INVAL, "ipg must be > 0");
-    if (b->ipg > 8192) return fail(e, MPX_E_UNSUPPORTED, "more than 8192 instances per group");
+    CK(step_shape(e, b));
     if ((uint64_t)b->n_groups * sizeof(uint32_t) > e->worklist.cap)
         return fail(e, MPX_E_INVAL, "n_groups exceeds mpx_config.max_groups");
     if (one_launch(e) && !mpx::step_one_launch_fits(e->cfg.n_replicas, b->ipg, e->cfg.kv_per_group))
@@ -786,7 +819,8 @@ int group_step_dev(mpx_engine* e, const mpx_group_batch* b, int64_t* d_totals, v
     }
     HIPCHK(e, mpx::launch_group_step(e->cfg.mode, e->cfg.n_replicas, e->cfg.kv_per_group, b,
                                      (uint32_t*)e->worklist.p, e->d_wcount, d_totals, e->d_err,
-                                     pick(e, stream), e->ev_fast0, e->ev_fast1, pslots(e)));
+                                     pick(e, stream), timed ? e->ev_fast0 : nullptr,
+                                     timed ? e->ev_fast1 : nullptr, pslots(e)));
     return MPX_OK;
 }
 }  // namespace
@@ -838,91 +872,77 @@ int mpx_group_step(mpx_engine* e, const mpx_group_batch* hb) {
             return fail(e, MPX_E_INVAL, "grp_rec_off not sorted");
     for (uint64_t i = 0; i < ni; ++i)
         if (hb->cmd_off[i + 1] < hb->cmd_off[i]) return fail(e, MPX_E_INVAL, "cmd_off not sorted");
+    CK(step_shape(e, hb));
     CK(begin(e));
-    // one device arena for the whole batch
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_recs = take(nr * 16), o_roff = take((G + 1) * 8), o_st = take(ni * 16),
-                 o_ci = take(G * 4), o_co = take(G * 4), o_ei = take(G * 4), o_eo = take(G * 4),
-                 o_pi = take(G * N * 4), o_po = take(G * N * 4), o_op = take(m), o_key = take(m * 8),
-                 o_val = take(m * 8), o_coff = take((ni + 1) * 4), o_has = take(ni),
-                 o_ret = take(m * 8), o_conf = take(m), o_kc = take(G * 4), o_kk = take(G * K * 8),
-                 o_kvv = take(G * K * 8), o_dec = take(ni), o_nd = take(G * 4);
-    GROW(e, e->b[0], off);
-    char* d = (char*)e->b[0].p;
-    mpx_group_batch db{};
-    db.n_groups = (uint32_t)G;
-    db.ipg = (uint32_t)ipg;
-    db.recs = (const mpx_accept_reply*)(d + o_recs);
-    db.grp_rec_off = (const uint64_t*)(d + o_roff);
-    db.st_in = (const mpx_inst_state*)(d + o_st);
-    db.st_out = (mpx_inst_state*)(d + o_st);
-    db.committed_in = (const int32_t*)(d + o_ci);
-    db.committed_out = (int32_t*)(d + o_co);
-    db.executed_in = (const int32_t*)(d + o_ei);
-    db.executed_out = (int32_t*)(d + o_eo);
-    db.peer_in = (const int32_t*)(d + o_pi);
-    db.peer_out = (int32_t*)(d + o_po);
-    db.op = (const uint8_t*)(d + o_op);
-    db.key = (const int64_t*)(d + o_key);
-    db.val = (const int64_t*)(d + o_val);
-    db.cmd_off = (const uint32_t*)(d + o_coff);
-    db.has_cmds = hb->has_cmds ? (const uint8_t*)(d + o_has) : nullptr;
-    db.ret = (int64_t*)(d + o_ret);
-    db.conf_prev = hb->conf_prev ? (uint8_t*)(d + o_conf) : nullptr;
-    db.kv_cnt_in = (const uint32_t*)(d + o_kc);
-    db.kv_key_in = (const int64_t*)(d + o_kk);
-    db.kv_val_in = (const int64_t*)(d + o_kvv);
-    db.kv_cnt_out = (uint32_t*)(d + o_kc);
-    db.kv_key_out = (int64_t*)(d + o_kk);
-    db.kv_val_out = (int64_t*)(d + o_kvv);
-    db.decided = hb->decided ? (uint8_t*)(d + o_dec) : nullptr;
-    db.n_decided = hb->n_decided ? (uint32_t*)(d + o_nd) : nullptr;
-    CK(h2d(e, d + o_recs, hb->recs, nr * 16));
-    CK(h2d(e, d + o_roff, hb->grp_rec_off, (G + 1) * 8));
-    CK(h2d(e, d + o_st, hb->st_in, ni * 16));
-    CK(h2d(e, d + o_ci, hb->committed_in, G * 4));
-    CK(h2d(e, d + o_ei, hb->executed_in, G * 4));
-    CK(h2d(e, d + o_pi, hb->peer_in, G * N * 4));
-    CK(h2d(e, d + o_op, hb->op, m));
-    CK(h2d(e, d + o_key, hb->key, m * 8));
-    CK(h2d(e, d + o_val, hb->val, m * 8));
-    CK(h2d(e, d + o_coff, hb->cmd_off, (ni + 1) * 4));
-    if (hb->has_cmds) CK(h2d(e, d + o_has, hb->has_cmds, ni));
-    CK(h2d(e, d + o_ret, hb->ret, m * 8));  // unexecuted commands keep the caller's values
-    if (hb->conf_prev) CK(h2d(e, d + o_conf, hb->conf_prev, m));
-    CK(h2d(e, d + o_kc, hb->kv_cnt_in, G * 4));
-    CK(h2d(e, d + o_kk, hb->kv_key_in, G * K * 8));
-    CK(h2d(e, d + o_kvv, hb->kv_val_in, G * K * 8));
-    if (ipg > 8192) return fail(e, MPX_E_UNSUPPORTED, "more than 8192 instances per group");
+    // unlike the _dev form, the host form takes more groups than mpx_config.max_groups
     if (G * sizeof(uint32_t) > e->worklist.cap) {
         GROW(e, e->worklist, G * sizeof(uint32_t));
         HIPCHK(e, hipMemsetAsync(e->worklist.p, 0, e->worklist.cap, e->stream));  // (slots)
     }
-    if (one_launch(e) && !mpx::step_one_launch_fits(N, (uint32_t)ipg, (uint32_t)K))
-        return fail(e, MPX_E_INVAL, "MPX_FLAG_STEP_ONE_LAUNCH: the batch shape fits no fast variant");
-    if (one_launch(e) && e->slots_dirty) {
-        HIPCHK(e, hipMemsetAsync(e->worklist.p, 0, e->worklist.cap, e->stream));
-        e->slots_dirty = false;
-    }
-    HIPCHK(e, mpx::launch_group_step(e->cfg.mode, N, (uint32_t)K, &db, (uint32_t*)e->worklist.p,
-                                     e->d_wcount, nullptr, e->d_err, e->stream, nullptr, nullptr,
-                                     pslots(e)));
-    CK(d2h(e, hb->st_out, d + o_st, ni * 16));
-    CK(d2h(e, hb->committed_out, d + o_co, G * 4));
-    CK(d2h(e, hb->executed_out, d + o_eo, G * 4));
-    CK(d2h(e, hb->peer_out, d + o_po, G * N * 4));
-    CK(d2h(e, hb->ret, d + o_ret, m * 8));
-    if (hb->conf_prev) CK(d2h(e, hb->conf_prev, d + o_conf, m));
-    CK(d2h(e, hb->kv_cnt_out, d + o_kc, G * 4));
-    CK(d2h(e, hb->kv_key_out, d + o_kk, G * K * 8));
-    CK(d2h(e, hb->kv_val_out, d + o_kvv, G * K * 8));
-    if (hb->decided) CK(d2h(e, hb->decided, d + o_dec, ni));
-    if (hb->n_decided) CK(d2h(e, hb->n_decided, d + o_nd, G * 4));
+    // in-place state (st, the KV tables) is one slot, in and out
+    Stage L(e);
+    const Slot s_recs = L.add(nr * sizeof(mpx_accept_reply)), s_roff = L.add((G + 1) * 8),
+               s_st = L.add(ni * sizeof(mpx_inst_state)), s_ci = L.add(G * 4),
+               s_co = L.add(G * 4), s_ei = L.add(G * 4), s_eo = L.add(G * 4),
+               s_pi = L.add(G * N * 4), s_po = L.add(G * N * 4), s_op = L.add(m),
+               s_key = L.add(m * 8), s_val = L.add(m * 8), s_coff = L.add((ni + 1) * 4),
+               s_has = L.add(hb->has_cmds ? ni : 0), s_ret = L.add(m * 8),
+               s_conf = L.add(hb->conf_prev ? m : 0), s_kc = L.add(G * 4),
+               s_kk = L.add(G * K * 8), s_kv = L.add(G * K * 8),
+               s_dec = L.add(hb->decided ? ni : 0), s_nd = L.add(hb->n_decided ? G * 4 : 0);
+    CK(L.commit());
+    mpx_group_batch db{};
+    db.n_groups = (uint32_t)G;
+    db.ipg = (uint32_t)ipg;
+    db.recs = L.at<mpx_accept_reply>(s_recs);
+    db.grp_rec_off = L.at<uint64_t>(s_roff);
+    db.st_in = db.st_out = L.at<mpx_inst_state>(s_st);
+    db.committed_in = L.at<int32_t>(s_ci);
+    db.committed_out = L.at<int32_t>(s_co);
+    db.executed_in = L.at<int32_t>(s_ei);
+    db.executed_out = L.at<int32_t>(s_eo);
+    db.peer_in = L.at<int32_t>(s_pi);
+    db.peer_out = L.at<int32_t>(s_po);
+    db.op = L.at<uint8_t>(s_op);
+    db.key = L.at<int64_t>(s_key);
+    db.val = L.at<int64_t>(s_val);
+    db.cmd_off = L.at<uint32_t>(s_coff);
+    db.has_cmds = L.at<uint8_t>(s_has, hb->has_cmds);
+    db.ret = L.at<int64_t>(s_ret);
+    db.conf_prev = L.at<uint8_t>(s_conf, hb->conf_prev);
+    db.kv_cnt_in = db.kv_cnt_out = L.at<uint32_t>(s_kc);
+    db.kv_key_in = db.kv_key_out = L.at<int64_t>(s_kk);
+    db.kv_val_in = db.kv_val_out = L.at<int64_t>(s_kv);
+    db.decided = L.at<uint8_t>(s_dec, hb->decided);
+    db.n_decided = L.at<uint32_t>(s_nd, hb->n_decided);
+    CK(L.in(s_recs, hb->recs));
+    CK(L.in(s_roff, hb->grp_rec_off));
+    CK(L.in(s_st, hb->st_in));
+    CK(L.in(s_ci, hb->committed_in));
+    CK(L.in(s_ei, hb->executed_in));
+    CK(L.in(s_pi, hb->peer_in));
+    CK(L.in(s_op, hb->op));
+    CK(L.in(s_key, hb->key));
+    CK(L.in(s_val, hb->val));
+    CK(L.in(s_coff, hb->cmd_off));
+    CK(L.in(s_has, hb->has_cmds));
+    CK(L.in(s_ret, hb->ret));  // unexecuted commands keep the caller's values
+    CK(L.in(s_conf, hb->conf_prev));
+    CK(L.in(s_kc, hb->kv_cnt_in));
+    CK(L.in(s_kk, hb->kv_key_in));
+    CK(L.in(s_kv, hb->kv_val_in));
+    CK(group_step_dev(e, &db, nullptr, e->stream, /*timed=*/false));
+    CK(L.out(s_st, hb->st_out));
+    CK(L.out(s_co, hb->committed_out));
+    CK(L.out(s_eo, hb->executed_out));
+    CK(L.out(s_po, hb->peer_out));
+    CK(L.out(s_ret, hb->ret));
+    CK(L.out(s_conf, hb->conf_prev));
+    CK(L.out(s_kc, hb->kv_cnt_out));
+    CK(L.out(s_kk, hb->kv_key_out));
+    CK(L.out(s_kv, hb->kv_val_out));
+    CK(L.out(s_dec, hb->decided));
+    CK(L.out(s_nd, hb->n_decided));
     return finish(e);
 }
 
@@ -1011,8 +1031,10 @@ int mpx_watermarks_allreduce(mpx_engine* e, int32_t* committed, int32_t* execute
     if (!e) return MPX_E_INVAL;
     if ((n_groups && (!committed || !executed))) return fail(e, MPX_E_INVAL, "null or invalid argument");
     CK(begin(e));
-    GROW(e, e->b[5], 2 * n_groups * 4);
-    int32_t* d = (int32_t*)e->b[5].p;
+    Stage L(e);
+    const Slot s_wm = L.add(2 * n_groups * 4);  // committed, then executed
+    CK(L.commit());
+    int32_t* d = L.at<int32_t>(s_wm);
     CK(h2d(e, d, committed, n_groups * 4));
     CK(h2d(e, d + n_groups, executed, n_groups * 4));
     CK(mpx_watermarks_allreduce_dev(e, d, n_groups, e->stream));
@@ -1024,11 +1046,8 @@ int mpx_watermarks_allreduce(mpx_engine* e, int32_t* committed, int32_t* execute
 // ---- §8(f) rank 1: peer stream framing + AcceptReply decode --------------------------------
 int mpx_decode_reserve(mpx_engine* e, size_t max_len) {
     if (!e) return MPX_E_INVAL;
-    if (max_len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
-    CK(begin(e));
-    GROW(e, e->decode_work, mpx::decode_work_bytes(max_len));
-    return finish(e);
+    CK(decode_limit(e, max_len));
+    return reserve(e, e->decode_work, mpx::decode_work_bytes(max_len));
 }
 
 int mpx_decode_peer_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
@@ -1037,12 +1056,9 @@ int mpx_decode_peer_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
     if (!e) return MPX_E_INVAL;
     if (!d_res || (len && !d_buf) || (ar_cap && !d_ar) || (other_cap && !d_other))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
-    if (e->decode_work.cap < mpx::decode_work_bytes(len))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_decode_peer_stream_dev: call mpx_decode_reserve(len) first (the dev "
-                    "entry point never allocates)");
+    CK(decode_limit(e, len));
+    CK(reserved(e, e->decode_work, mpx::decode_work_bytes(len), "mpx_decode_peer_stream_dev",
+                "mpx_decode_reserve(len)"));
     HIPCHK(e, mpx::launch_decode_peer_stream(d_buf, len, d_ar, ar_cap, d_other, other_cap, d_res,
                                              e->decode_work.p, e->decode_work.cap,
                                              pick(e, stream)));
@@ -1055,25 +1071,24 @@ int mpx_decode_peer_stream(mpx_engine* e, const uint8_t* buf, size_t len, mpx_ac
     if (!e) return MPX_E_INVAL;
     if (!res || (len && !buf) || (ar_cap && !ar) || (other_cap && !other))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
+    CK(decode_limit(e, len));
     CK(begin(e));
-    GROW(e, e->dec[0], len);
-    GROW(e, e->dec[1], ar_cap * sizeof(mpx_accept_reply));
-    GROW(e, e->dec[2], other_cap * sizeof(mpx_peer_frame));
-    GROW(e, e->dec[3], sizeof(mpx_decode_result));
     GROW(e, e->decode_work, mpx::decode_work_bytes(len));
-    CK(h2d(e, e->dec[0].p, buf, len));
-    CK(mpx_decode_peer_stream_dev(e, (const uint8_t*)e->dec[0].p, len,
-                                  (mpx_accept_reply*)e->dec[1].p, ar_cap,
-                                  (mpx_peer_frame*)e->dec[2].p, other_cap,
-                                  (mpx_decode_result*)e->dec[3].p, e->stream));
-    CK(d2h(e, res, e->dec[3].p, sizeof(mpx_decode_result)));
+    Stage L(e);
+    const Slot s_buf = L.add(len), s_ar = L.add(ar_cap * sizeof(mpx_accept_reply)),
+               s_oth = L.add(other_cap * sizeof(mpx_peer_frame)),
+               s_res = L.add(sizeof(mpx_decode_result));
+    CK(L.commit());
+    CK(L.in(s_buf, buf));
+    CK(mpx_decode_peer_stream_dev(e, L.at<uint8_t>(s_buf), len, L.at<mpx_accept_reply>(s_ar),
+                                  ar_cap, L.at<mpx_peer_frame>(s_oth), other_cap,
+                                  L.at<mpx_decode_result>(s_res), e->stream));
+    CK(L.out(s_res, res));
     CK(finish(e));
-    CK(d2h(e, ar, e->dec[1].p, std::min<uint64_t>(res->n_accept_replies, ar_cap) *
-                                   sizeof(mpx_accept_reply)));
-    CK(d2h(e, other, e->dec[2].p, std::min<uint64_t>(res->n_other, other_cap) *
-                                      sizeof(mpx_peer_frame)));
+    // the records the call wrote (the result counts past the caller's capacities)
+    CK(L.out(s_ar, ar, std::min<uint64_t>(res->n_accept_replies, ar_cap) *
+                           sizeof(mpx_accept_reply)));
+    CK(L.out(s_oth, other, std::min<uint64_t>(res->n_other, other_cap) * sizeof(mpx_peer_frame)));
     return finish(e);
 }
 
@@ -1082,33 +1097,32 @@ namespace {
 size_t prep_rec_bytes(const mpx_engine* e) {
     return e->cfg.mode == MPX_MODE_MIN ? sizeof(mpx_prepare_reply_min) : sizeof(mpx_prepare_reply);
 }
+// the argument rules both forms share (buf / res: host or device pointers alike)
+int decode_stream_args(mpx_engine* e, const uint8_t* buf, size_t len, const mpx_decode_out* out,
+                       const mpx_stream_result* res) {
+    if (!out || !res || (len && !buf) || (out->ar_cap && !out->ar) ||
+        (out->prep_cap && !out->prep) || (out->var_cap && !out->var) ||
+        (out->other_cap && !out->other))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    return decode_limit(e, len);
+}
 }  // namespace
 
 int mpx_decode_stream_reserve(mpx_engine* e, size_t max_len) {
     if (!e) return MPX_E_INVAL;
-    if (max_len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
-    CK(begin(e));
-    GROW(e, e->stream_work, mpx::stream_work_bytes(max_len));
-    return finish(e);
+    CK(decode_limit(e, max_len));
+    return reserve(e, e->stream_work, mpx::stream_work_bytes(max_len));
 }
 
 int mpx_decode_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len, size_t start,
                           const mpx_decode_out* out, mpx_stream_result* d_res, void* stream) {
     if (!e) return MPX_E_INVAL;
-    if (!out || !d_res || (len && !d_buf) || (out->ar_cap && !out->ar) ||
-        (out->prep_cap && !out->prep) || (out->var_cap && !out->var) ||
-        (out->other_cap && !out->other))
-        return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
+    CK(decode_stream_args(e, d_buf, len, out, d_res));
     if (start > len) return fail(e, MPX_E_INVAL, "start is past the end of the buffer");
     if ((uintptr_t)d_buf % 16)
         return fail(e, MPX_E_INVAL, "d_buf must be 16-byte aligned (tiles load 16 B vectors)");
-    if (e->stream_work.cap < mpx::stream_work_bytes(len))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_decode_stream_dev: call mpx_decode_stream_reserve(len) first (the dev "
-                    "entry point never allocates)");
+    CK(reserved(e, e->stream_work, mpx::stream_work_bytes(len), "mpx_decode_stream_dev",
+                "mpx_decode_stream_reserve(len)"));
     const mpx::StreamOuts o{out->ar, out->ar_cap, out->prep, out->prep_cap, out->var,
                             out->var_cap, out->other, out->other_cap};
     HIPCHK(e, mpx::launch_decode_stream(e->cfg.mode, 0, d_buf, len, start, o, d_res,
@@ -1119,36 +1133,32 @@ int mpx_decode_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len, size_
 int mpx_decode_stream(mpx_engine* e, const uint8_t* buf, size_t len, const mpx_decode_out* out,
                       mpx_stream_result* res) {
     if (!e) return MPX_E_INVAL;
-    if (!out || !res || (len && !buf) || (out->ar_cap && !out->ar) ||
-        (out->prep_cap && !out->prep) || (out->var_cap && !out->var) ||
-        (out->other_cap && !out->other))
-        return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (len > MPX_DECODE_MAX_BYTES)
-        return fail(e, MPX_E_UNSUPPORTED, "decode buffers are limited to 2^31-1 bytes per call");
+    CK(decode_stream_args(e, buf, len, out, res));
     const size_t pb = prep_rec_bytes(e);
     CK(begin(e));
-    GROW(e, e->sd[0], len);
-    GROW(e, e->sd[1], out->ar_cap * sizeof(mpx_accept_reply));
-    GROW(e, e->sd[2], out->prep_cap * pb);
-    GROW(e, e->sd[3], out->var_cap * sizeof(mpx_var_frame));
-    GROW(e, e->sd[4], out->other_cap * sizeof(mpx_peer_frame));
-    GROW(e, e->sd[5], sizeof(mpx_stream_result));
     GROW(e, e->stream_work, mpx::stream_work_bytes(len));
-    CK(h2d(e, e->sd[0].p, buf, len));
-    const mpx_decode_out d{(mpx_accept_reply*)e->sd[1].p, out->ar_cap, e->sd[2].p, out->prep_cap,
-                           (mpx_var_frame*)e->sd[3].p, out->var_cap,
-                           (mpx_peer_frame*)e->sd[4].p, out->other_cap};
+    Stage L(e);
+    const Slot s_buf = L.add(len), s_ar = L.add(out->ar_cap * sizeof(mpx_accept_reply)),
+               s_prep = L.add(out->prep_cap * pb),
+               s_var = L.add(out->var_cap * sizeof(mpx_var_frame)),
+               s_oth = L.add(out->other_cap * sizeof(mpx_peer_frame)),
+               s_res = L.add(sizeof(mpx_stream_result));
+    CK(L.commit());
+    CK(L.in(s_buf, buf));
+    const mpx_decode_out d{L.at<mpx_accept_reply>(s_ar), out->ar_cap, L.at<void>(s_prep),
+                           out->prep_cap, L.at<mpx_var_frame>(s_var), out->var_cap,
+                           L.at<mpx_peer_frame>(s_oth), out->other_cap};
     mpx_stream_result r;
     memset(&r, 0, sizeof(r));
-    CK(h2d(e, e->sd[5].p, &r, sizeof(r)));
+    CK(L.in(s_res, &r));
     // one call per frame longer than the in-map window (MPX_DECODE_LONG); after one, windows
     // of the buffer (a PARTIAL stop at a window's end just continues) keep each call short
     size_t start = 0, window = len;
     for (;;) {
         const size_t end = std::min(len, start + window);
-        CK(mpx_decode_stream_dev(e, (const uint8_t*)e->sd[0].p, end, start, &d,
-                                 (mpx_stream_result*)e->sd[5].p, e->stream));
-        CK(d2h(e, &r, e->sd[5].p, sizeof(r)));
+        CK(mpx_decode_stream_dev(e, L.at<uint8_t>(s_buf), end, start, &d,
+                                 L.at<mpx_stream_result>(s_res), e->stream));
+        CK(L.out(s_res, &r));
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (r.stop_reason == MPX_DECODE_LONG && r.next <= len) {
             start = r.next;
@@ -1164,23 +1174,20 @@ int mpx_decode_stream(mpx_engine* e, const uint8_t* buf, size_t len, const mpx_d
         }
     }
     *res = r;
-    CK(d2h(e, out->ar, e->sd[1].p, std::min<uint64_t>(r.n_accept_replies, out->ar_cap) *
-                                      sizeof(mpx_accept_reply)));
-    CK(d2h(e, out->prep, e->sd[2].p, std::min<uint64_t>(r.n_prepare_replies, out->prep_cap) * pb));
-    CK(d2h(e, out->var, e->sd[3].p, std::min<uint64_t>(r.n_var, out->var_cap) *
-                                       sizeof(mpx_var_frame)));
-    CK(d2h(e, out->other, e->sd[4].p, std::min<uint64_t>(r.n_other, out->other_cap) *
-                                         sizeof(mpx_peer_frame)));
+    CK(L.out(s_ar, out->ar, std::min<uint64_t>(r.n_accept_replies, out->ar_cap) *
+                                sizeof(mpx_accept_reply)));
+    CK(L.out(s_prep, out->prep, std::min<uint64_t>(r.n_prepare_replies, out->prep_cap) * pb));
+    CK(L.out(s_var, out->var, std::min<uint64_t>(r.n_var, out->var_cap) * sizeof(mpx_var_frame)));
+    CK(L.out(s_oth, out->other, std::min<uint64_t>(r.n_other, out->other_cap) *
+                                    sizeof(mpx_peer_frame)));
     return finish(e);
 }
 
 // ---- §8(f) rank 2: client reply fan-out -----------------------------------------------------
 int mpx_encode_replies_reserve(mpx_engine* e, size_t max_n) {
     if (!e) return MPX_E_INVAL;
-    if (max_n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
-    CK(begin(e));
-    GROW(e, e->fan_work, mpx::fanout_work_bytes(max_n));
-    return finish(e);
+    CK(reply_limit(e, max_n));
+    return reserve(e, e->fan_work, mpx::fanout_work_bytes(max_n));
 }
 
 int mpx_encode_replies_dev(mpx_engine* e, const mpx_reply_rec* d_recs, size_t n,
@@ -1188,11 +1195,9 @@ int mpx_encode_replies_dev(mpx_engine* e, const mpx_reply_rec* d_recs, size_t n,
                            uint64_t* d_client_off, void* stream) {
     if (!e) return MPX_E_INVAL;
     if (!n_clients || !d_client_off || (n && (!d_recs || !d_out))) return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
-    if (e->fan_work.cap < mpx::fanout_work_bytes(n))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_encode_replies_dev: call mpx_encode_replies_reserve(n) first (the dev "
-                    "entry point never allocates)");
+    CK(reply_limit(e, n));
+    CK(reserved(e, e->fan_work, mpx::fanout_work_bytes(n), "mpx_encode_replies_dev",
+                "mpx_encode_replies_reserve(n)"));
     HIPCHK(e, mpx::launch_encode_replies(d_recs, n, n_clients, ok, leader, d_out, d_client_off,
                                          e->fan_work.p, e->fan_work.cap, e->d_err,
                                          pick(e, stream)));
@@ -1203,38 +1208,44 @@ int mpx_encode_replies(mpx_engine* e, const mpx_reply_rec* recs, size_t n, uint3
                        uint8_t ok, int32_t leader, uint8_t* out, uint64_t* client_off) {
     if (!e) return MPX_E_INVAL;
     if (!n_clients || !client_off || (n && (!recs || !out))) return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    CK(reply_limit(e, n));
     CK(begin(e));
-    GROW(e, e->fan[0], n * sizeof(mpx_reply_rec));
-    GROW(e, e->fan[1], n * MPX_PROPOSE_REPLY_BYTES);
-    GROW(e, e->fan[2], ((size_t)n_clients + 1) * sizeof(uint64_t));
     GROW(e, e->fan_work, mpx::fanout_work_bytes(n));
-    CK(h2d(e, e->fan[0].p, recs, n * sizeof(mpx_reply_rec)));
-    CK(mpx_encode_replies_dev(e, (const mpx_reply_rec*)e->fan[0].p, n, n_clients, ok, leader,
-                              (uint8_t*)e->fan[1].p, (uint64_t*)e->fan[2].p, e->stream));
-    CK(d2h(e, out, e->fan[1].p, n * MPX_PROPOSE_REPLY_BYTES));
-    CK(d2h(e, client_off, e->fan[2].p, ((size_t)n_clients + 1) * sizeof(uint64_t)));
+    Stage L(e);
+    const Slot s_rec = L.add(n * sizeof(mpx_reply_rec)), s_out = L.add(n * MPX_PROPOSE_REPLY_BYTES),
+               s_off = L.add(((size_t)n_clients + 1) * sizeof(uint64_t));
+    CK(L.commit());
+    CK(L.in(s_rec, recs));
+    CK(mpx_encode_replies_dev(e, L.at<mpx_reply_rec>(s_rec), n, n_clients, ok, leader,
+                              L.at<uint8_t>(s_out), L.at<uint64_t>(s_off), e->stream));
+    CK(L.out(s_out, out));
+    CK(L.out(s_off, client_off));
     int rc = finish(e);
     if (rc == MPX_E_INVAL) return fail(e, MPX_E_INVAL, "a reply names a client >= n_clients");
     return rc;
 }
 
 // ---- the acceptor side: handleAccept and the AcceptReply bytes ------------------------------
+namespace {
+// the sizes both forms take (the host form checks them before it allocates)
+int accept_handle_shape(mpx_engine* e, size_t n, size_t n_inst, size_t n_groups, uint32_t ipg) {
+    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
+        n_inst > (1ull << 32))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    return record_limit(e, n);
+}
+}  // namespace
+
 int mpx_accept_handle_dev(mpx_engine* e, const mpx_accept_msg* d_msgs, size_t n,
                           const mpx_acceptor_state* d_st_in, mpx_acceptor_state* d_st_out,
                           size_t n_inst, int32_t inst_base, const mpx_acceptor_group* d_groups,
                           size_t n_groups, uint32_t ipg, mpx_accept_reply* d_replies,
                           int32_t* d_reply_to, uint8_t* d_effect, void* stream) {
     if (!e) return MPX_E_INVAL;
-    if (!mpx::launch_accept_handle)
-        return fail(e, MPX_E_UNSUPPORTED, "mpx_accept_handle: the acceptor kernels are not built in");
     if ((n && (!d_msgs || !d_replies || !d_reply_to || !d_effect)) ||
         (n_inst && (!d_st_in || !d_st_out)) || !d_groups)
         return fail(e, MPX_E_INVAL, "null argument");
-    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
-        n_inst > (1ull << 32))
-        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
-    if (n >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "more than 2^32-2 records");
+    CK(accept_handle_shape(e, n, n_inst, n_groups, ipg));
     HIPCHK(e, mpx::launch_accept_handle(e->cfg.mode, d_msgs, n, d_st_in, d_st_out, n_inst,
                                         inst_base, d_groups, n_groups, ipg, e->cfg.n_replicas,
                                         d_replies, d_reply_to, d_effect, e->d_err,
@@ -1247,33 +1258,29 @@ int mpx_accept_handle(mpx_engine* e, const mpx_accept_msg* msgs, size_t n, mpx_a
                       size_t n_groups, uint32_t ipg, mpx_accept_reply* replies, int32_t* reply_to,
                       uint8_t* effect) {
     if (!e) return MPX_E_INVAL;
-    if (!mpx::launch_accept_handle)
-        return fail(e, MPX_E_UNSUPPORTED, "mpx_accept_handle: the acceptor kernels are not built in");
     if ((n && (!msgs || !replies || !reply_to || !effect)) || (n_inst && !st) || !groups)
         return fail(e, MPX_E_INVAL, "null argument");
-    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
-        n_inst > (1ull << 32))
-        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    CK(accept_handle_shape(e, n, n_inst, n_groups, ipg));
     CK(begin(e));
-    GROW(e, e->ah[0], n * sizeof(mpx_accept_msg));
-    GROW(e, e->ah[1], n_inst * sizeof(mpx_acceptor_state));
-    GROW(e, e->ah[2], n_groups * sizeof(mpx_acceptor_group));
-    GROW(e, e->ah[3], n * sizeof(mpx_accept_reply));
-    GROW(e, e->ah[4], n * sizeof(int32_t));
-    GROW(e, e->ah[5], n);
-    CK(h2d(e, e->ah[0].p, msgs, n * sizeof(mpx_accept_msg)));
-    CK(h2d(e, e->ah[1].p, st, n_inst * sizeof(mpx_acceptor_state)));
-    CK(h2d(e, e->ah[2].p, groups, n_groups * sizeof(mpx_acceptor_group)));
-    CK(mpx_accept_handle_dev(e, (const mpx_accept_msg*)e->ah[0].p, n,
-                             (const mpx_acceptor_state*)e->ah[1].p,
-                             (mpx_acceptor_state*)e->ah[1].p, n_inst, inst_base,
-                             (const mpx_acceptor_group*)e->ah[2].p, n_groups, ipg,
-                             (mpx_accept_reply*)e->ah[3].p, (int32_t*)e->ah[4].p,
-                             (uint8_t*)e->ah[5].p, e->stream));
-    CK(d2h(e, st, e->ah[1].p, n_inst * sizeof(mpx_acceptor_state)));
-    CK(d2h(e, replies, e->ah[3].p, n * sizeof(mpx_accept_reply)));
-    CK(d2h(e, reply_to, e->ah[4].p, n * sizeof(int32_t)));
-    CK(d2h(e, effect, e->ah[5].p, n));
+    Stage L(e);
+    const Slot s_msg = L.add(n * sizeof(mpx_accept_msg)),
+               s_st = L.add(n_inst * sizeof(mpx_acceptor_state)),
+               s_grp = L.add(n_groups * sizeof(mpx_acceptor_group)),
+               s_rep = L.add(n * sizeof(mpx_accept_reply)), s_to = L.add(n * sizeof(int32_t)),
+               s_eff = L.add(n);
+    CK(L.commit());
+    CK(L.in(s_msg, msgs));
+    CK(L.in(s_st, st));
+    CK(L.in(s_grp, groups));
+    mpx_acceptor_state* d_st = L.at<mpx_acceptor_state>(s_st);
+    CK(mpx_accept_handle_dev(e, L.at<mpx_accept_msg>(s_msg), n, d_st, d_st, n_inst, inst_base,
+                             L.at<mpx_acceptor_group>(s_grp), n_groups, ipg,
+                             L.at<mpx_accept_reply>(s_rep), L.at<int32_t>(s_to),
+                             L.at<uint8_t>(s_eff), e->stream));
+    CK(L.out(s_st, st));
+    CK(L.out(s_rep, replies));
+    CK(L.out(s_to, reply_to));
+    CK(L.out(s_eff, effect));
     return finish(e);
 }
 
@@ -1283,30 +1290,21 @@ static size_t accept_reply_frame(const mpx_engine* e) {
 
 int mpx_encode_accept_replies_reserve(mpx_engine* e, size_t max_n) {
     if (!e) return MPX_E_INVAL;
-    if (!mpx::accept_replies_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED,
-                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
-    if (max_n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
-    CK(begin(e));
-    GROW(e, e->are_work, mpx::accept_replies_work_bytes(max_n));
-    return finish(e);
+    CK(reply_limit(e, max_n));
+    return reserve(e, e->are_work, mpx::accept_replies_work_bytes(max_n));
 }
 
 int mpx_encode_accept_replies_dev(mpx_engine* e, const mpx_accept_reply* d_replies,
                                   const int32_t* d_reply_to, size_t n, uint32_t n_dest,
                                   uint8_t* d_out, uint64_t* d_dest_off, void* stream) {
     if (!e) return MPX_E_INVAL;
-    if (!mpx::launch_encode_accept_replies || !mpx::accept_replies_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED,
-                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
     if (!n_dest || n_dest > MPX_MAX_REPLICAS || !d_dest_off ||
         (n && (!d_replies || !d_reply_to || !d_out)))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
-    if (n && e->are_work.cap < mpx::accept_replies_work_bytes(n))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_encode_accept_replies_dev: call mpx_encode_accept_replies_reserve(n) "
-                    "first (the dev entry point never allocates)");
+    CK(reply_limit(e, n));
+    // (an empty call uses no scratch)
+    CK(reserved(e, e->are_work, n ? mpx::accept_replies_work_bytes(n) : 0,
+                "mpx_encode_accept_replies_dev", "mpx_encode_accept_replies_reserve(n)"));
     HIPCHK(e, mpx::launch_encode_accept_replies(e->cfg.mode, d_replies, d_reply_to, n, n_dest,
                                                 d_out, d_dest_off, e->are_work.p,
                                                 e->are_work.cap, e->d_err, pick(e, stream)));
@@ -1317,32 +1315,29 @@ int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
                               const int32_t* reply_to, size_t n, uint32_t n_dest, uint8_t* out,
                               uint64_t* dest_off) {
     if (!e) return MPX_E_INVAL;
-    if (!mpx::launch_encode_accept_replies || !mpx::accept_replies_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED,
-                    "mpx_encode_accept_replies: the acceptor kernels are not built in");
     if (!n_dest || n_dest > MPX_MAX_REPLICAS || !dest_off || (n && (!replies || !reply_to || !out)))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (n >= (1ull << 32)) return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 replies per call");
+    CK(reply_limit(e, n));
     const size_t frame = accept_reply_frame(e);
     CK(begin(e));
-    GROW(e, e->are[0], n * sizeof(mpx_accept_reply));
-    GROW(e, e->are[1], n * sizeof(int32_t));
-    GROW(e, e->are[2], n * frame);
-    GROW(e, e->are[3], ((size_t)n_dest + 1) * sizeof(uint64_t));
     if (n) GROW(e, e->are_work, mpx::accept_replies_work_bytes(n));
-    CK(h2d(e, e->are[0].p, replies, n * sizeof(mpx_accept_reply)));
-    CK(h2d(e, e->are[1].p, reply_to, n * sizeof(int32_t)));
-    CK(mpx_encode_accept_replies_dev(e, (const mpx_accept_reply*)e->are[0].p,
-                                     (const int32_t*)e->are[1].p, n, n_dest,
-                                     (uint8_t*)e->are[2].p, (uint64_t*)e->are[3].p, e->stream));
-    CK(d2h(e, dest_off, e->are[3].p, ((size_t)n_dest + 1) * sizeof(uint64_t)));
+    Stage L(e);
+    const Slot s_rep = L.add(n * sizeof(mpx_accept_reply)), s_to = L.add(n * sizeof(int32_t)),
+               s_out = L.add(n * frame), s_off = L.add(((size_t)n_dest + 1) * sizeof(uint64_t));
+    CK(L.commit());
+    CK(L.in(s_rep, replies));
+    CK(L.in(s_to, reply_to));
+    CK(mpx_encode_accept_replies_dev(e, L.at<mpx_accept_reply>(s_rep), L.at<int32_t>(s_to), n,
+                                     n_dest, L.at<uint8_t>(s_out), L.at<uint64_t>(s_off),
+                                     e->stream));
+    CK(L.out(s_off, dest_off));
     const int rc = finish(e);
     if (rc == MPX_E_INVAL) return fail(e, MPX_E_INVAL, "a reply names a destination >= n_dest");
     if (rc) return rc;
     // the frames written: skipped slots leave the rest of out untouched
     const uint64_t total = dest_off[n_dest];
     if (total > n * frame) return fail(e, MPX_E_HIP, "mpx_encode_accept_replies: bad offsets");
-    CK(d2h(e, out, e->are[2].p, total));
+    CK(L.out(s_out, out, total));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return MPX_OK;
 }
@@ -1350,11 +1345,15 @@ int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
 // ---- §8(f) ranks 3/4: instance-log encoding -------------------------------------------------
 size_t mpx_encode_log_bound(size_t n, size_t m) { return (size_t)mpx::logenc_max_bytes(n, m); }
 
+static int log_format(mpx_engine* e, int format) {
+    if (format != MPX_LOG_CATCHUP && format != MPX_LOG_DURABLE)
+        return fail(e, MPX_E_INVAL, "unknown log format");
+    return MPX_OK;
+}
+
 int mpx_encode_log_reserve(mpx_engine* e, size_t max_n, size_t max_m) {
     if (!e) return MPX_E_INVAL;
-    CK(begin(e));
-    GROW(e, e->log_work, mpx::logenc_work_bytes(max_n, max_m));
-    return finish(e);
+    return reserve(e, e->log_work, mpx::logenc_work_bytes(max_n, max_m));
 }
 
 int mpx_encode_log_dev(mpx_engine* e, int format, const mpx_log_rec* d_recs, size_t n,
@@ -1364,12 +1363,9 @@ int mpx_encode_log_dev(mpx_engine* e, int format, const mpx_log_rec* d_recs, siz
     if (!e) return MPX_E_INVAL;
     if (!d_rec_off || (n && (!d_recs || !d_cmd_off || !d_out)) || (m && (!d_op || !d_key || !d_val)))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (format != MPX_LOG_CATCHUP && format != MPX_LOG_DURABLE)
-        return fail(e, MPX_E_INVAL, "unknown log format");
-    if (e->log_work.cap < mpx::logenc_work_bytes(n, m))
-        return fail(e, MPX_E_INVAL,
-                    "mpx_encode_log_dev: call mpx_encode_log_reserve(n, m) first (the dev entry "
-                    "point never allocates)");
+    CK(log_format(e, format));
+    CK(reserved(e, e->log_work, mpx::logenc_work_bytes(n, m), "mpx_encode_log_dev",
+                "mpx_encode_log_reserve(n, m)"));
     HIPCHK(e, mpx::launch_encode_log(format, d_recs, n, d_cmd_off, d_op, d_key, d_val, m, d_out,
                                      d_rec_off, e->log_work.p, e->log_work.cap, pick(e, stream)));
     return MPX_OK;
@@ -1382,34 +1378,31 @@ int mpx_encode_log(mpx_engine* e, int format, const mpx_log_rec* recs, size_t n,
     if (!e) return MPX_E_INVAL;
     if (!rec_off || (n && (!recs || !cmd_off)) || (m && (!op || !key || !val)) || (out_cap && !out))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
-    if (format != MPX_LOG_CATCHUP && format != MPX_LOG_DURABLE)
-        return fail(e, MPX_E_INVAL, "unknown log format");
+    CK(log_format(e, format));
     for (size_t i = 0; i < n; ++i)  // the device kernels trust the offsets
         if (cmd_off[i] > cmd_off[i + 1] || cmd_off[i + 1] > m)
             return fail(e, MPX_E_INVAL, "cmd_off must be non-decreasing and <= m");
     const size_t bound = mpx::logenc_max_bytes(n, m);
     CK(begin(e));
-    GROW(e, e->lg[0], n * sizeof(mpx_log_rec));
-    GROW(e, e->lg[1], (n + 1) * 8);
-    GROW(e, e->lg[2], m);
-    GROW(e, e->lg[3], m * 8);
-    GROW(e, e->lg[4], m * 8);
-    GROW(e, e->lg[5], bound);
-    GROW(e, e->lg[6], (n + 1) * 8);
     GROW(e, e->log_work, mpx::logenc_work_bytes(n, m));
-    CK(h2d(e, e->lg[0].p, recs, n * sizeof(mpx_log_rec)));
-    if (n) CK(h2d(e, e->lg[1].p, cmd_off, (n + 1) * 8));
-    CK(h2d(e, e->lg[2].p, op, m));
-    CK(h2d(e, e->lg[3].p, key, m * 8));
-    CK(h2d(e, e->lg[4].p, val, m * 8));
-    CK(mpx_encode_log_dev(e, format, (const mpx_log_rec*)e->lg[0].p, n,
-                          (const uint64_t*)e->lg[1].p, (const uint8_t*)e->lg[2].p,
-                          (const int64_t*)e->lg[3].p, (const int64_t*)e->lg[4].p, m,
-                          (uint8_t*)e->lg[5].p, (uint64_t*)e->lg[6].p, e->stream));
-    CK(d2h(e, rec_off, e->lg[6].p, (n + 1) * 8));
+    Stage L(e);
+    // (cmd_off may be null when n == 0: nothing of it is read then)
+    const Slot s_rec = L.add(n * sizeof(mpx_log_rec)), s_coff = L.add(n ? (n + 1) * 8 : 0),
+               s_op = L.add(m), s_key = L.add(m * 8), s_val = L.add(m * 8), s_out = L.add(bound),
+               s_roff = L.add((n + 1) * 8);
+    CK(L.commit());
+    CK(L.in(s_rec, recs));
+    CK(L.in(s_coff, cmd_off));
+    CK(L.in(s_op, op));
+    CK(L.in(s_key, key));
+    CK(L.in(s_val, val));
+    CK(mpx_encode_log_dev(e, format, L.at<mpx_log_rec>(s_rec), n, L.at<uint64_t>(s_coff),
+                          L.at<uint8_t>(s_op), L.at<int64_t>(s_key), L.at<int64_t>(s_val), m,
+                          L.at<uint8_t>(s_out), L.at<uint64_t>(s_roff), e->stream));
+    CK(L.out(s_roff, rec_off));
     CK(finish(e));
     if (rec_off[n] > out_cap) return fail(e, MPX_E_INVAL, "out_cap is smaller than the encoding");
-    CK(d2h(e, out, e->lg[5].p, rec_off[n]));
+    CK(L.out(s_out, out, rec_off[n]));
     return finish(e);
 }
 
@@ -1453,9 +1446,7 @@ int mpx_replay_durable_reserve(mpx_engine* e, size_t max_len, int32_t inst_cap) 
     if (!e) return MPX_E_INVAL;
     if (inst_cap < 0) return fail(e, MPX_E_INVAL, "inst_cap must be >= 0");
     const size_t n = max_len / MPX_DURABLE_REC_BYTES;
-    CK(begin(e));
-    GROW(e, e->replay_work, mpx::replay_work_bytes(n, inst_cap));
-    return finish(e);
+    return reserve(e, e->replay_work, mpx::replay_work_bytes(n, inst_cap));
 }
 
 int mpx_replay_durable(mpx_engine* e, const uint8_t* log, size_t len, int32_t inst_cap,
@@ -1467,28 +1458,26 @@ int mpx_replay_durable(mpx_engine* e, const uint8_t* log, size_t len, int32_t in
     CK(replay_args(e, len, inst_cap, rec_base, &n));
     if (n && (!log || !recs || !op || !key || !val)) return fail(e, MPX_E_INVAL, "null argument");
     CK(begin(e));
-    GROW(e, e->rp[0], len);
-    GROW(e, e->rp[1], n * sizeof(mpx_log_rec));
-    GROW(e, e->rp[2], n);
-    GROW(e, e->rp[3], n * 8);
-    GROW(e, e->rp[4], n * 8);
-    GROW(e, e->rp[5], (size_t)inst_cap * 4);
-    GROW(e, e->rp[6], 2 * sizeof(int32_t));
     GROW(e, e->replay_work, mpx::replay_work_bytes(n, inst_cap));
-    CK(h2d(e, e->rp[0].p, log, len));
-    CK(h2d(e, e->rp[5].p, last_rec, (size_t)inst_cap * 4));
-    CK(h2d(e, e->rp[6].p, scalars, 2 * sizeof(int32_t)));
-    if (n)
-        CK(mpx_replay_durable_dev(e, (const uint8_t*)e->rp[0].p, len, inst_cap, rec_base,
-                                  (mpx_log_rec*)e->rp[1].p, (uint8_t*)e->rp[2].p,
-                                  (int64_t*)e->rp[3].p, (int64_t*)e->rp[4].p,
-                                  (int32_t*)e->rp[5].p, (int32_t*)e->rp[6].p, e->stream));
-    CK(d2h(e, recs, e->rp[1].p, n * sizeof(mpx_log_rec)));
-    CK(d2h(e, op, e->rp[2].p, n));
-    CK(d2h(e, key, e->rp[3].p, n * 8));
-    CK(d2h(e, val, e->rp[4].p, n * 8));
-    CK(d2h(e, last_rec, e->rp[5].p, (size_t)inst_cap * 4));
-    CK(d2h(e, scalars, e->rp[6].p, 2 * sizeof(int32_t)));
+    Stage L(e);
+    const Slot s_log = L.add(len), s_rec = L.add(n * sizeof(mpx_log_rec)), s_op = L.add(n),
+               s_key = L.add(n * 8), s_val = L.add(n * 8), s_last = L.add((size_t)inst_cap * 4),
+               s_sc = L.add(2 * sizeof(int32_t));
+    CK(L.commit());
+    CK(L.in(s_log, log));
+    CK(L.in(s_last, last_rec));
+    CK(L.in(s_sc, scalars));
+    if (n)  // (an empty log still round-trips last_rec and scalars)
+        CK(mpx_replay_durable_dev(e, L.at<uint8_t>(s_log), len, inst_cap, rec_base,
+                                  L.at<mpx_log_rec>(s_rec), L.at<uint8_t>(s_op),
+                                  L.at<int64_t>(s_key), L.at<int64_t>(s_val),
+                                  L.at<int32_t>(s_last), L.at<int32_t>(s_sc), e->stream));
+    CK(L.out(s_rec, recs));
+    CK(L.out(s_op, op));
+    CK(L.out(s_key, key));
+    CK(L.out(s_val, val));
+    CK(L.out(s_last, last_rec));
+    CK(L.out(s_sc, scalars));
     int rc = finish(e);
     if (rc == MPX_E_NIL_INSTANCE)
         return fail(e, rc, "a durable record's instNo is outside [0, inst_cap)");

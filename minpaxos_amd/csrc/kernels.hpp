@@ -188,16 +188,14 @@ hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t
                                  hipStream_t stream);
 
 // ---- the acceptor side (mpx_accept_handle, mpx_encode_accept_replies; acceptor.hip) ---------
-// Weak: CPU builds of engine.cpp that link a launcher set without them still link and load, and
-// the entry points answer MPX_E_UNSUPPORTED there.
 // One launch: no scratch, no control words (the step reduces no scalars).
-__attribute__((weak)) hipError_t launch_accept_handle(
+hipError_t launch_accept_handle(
     int mode, const mpx_accept_msg* msgs, uint64_t n, const mpx_acceptor_state* st_in,
     mpx_acceptor_state* st_out, uint64_t n_inst, int32_t base, const mpx_acceptor_group* groups,
     uint64_t n_groups, uint32_t ipg, int32_t nrep, mpx_accept_reply* replies, int32_t* reply_to,
     uint8_t* effect, uint32_t* err, hipStream_t stream);
-__attribute__((weak)) uint64_t accept_replies_work_bytes(uint64_t n);
-__attribute__((weak)) hipError_t launch_encode_accept_replies(
+uint64_t accept_replies_work_bytes(uint64_t n);
+hipError_t launch_encode_accept_replies(
     int mode, const mpx_accept_reply* replies, const int32_t* reply_to, uint64_t n,
     uint32_t n_dest, uint8_t* out, uint64_t* dest_off, void* work, uint64_t work_bytes,
     uint32_t* err, hipStream_t stream);

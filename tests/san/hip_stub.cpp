@@ -4,7 +4,8 @@
 // (so stream and event order hold trivially) and events carry a host timestamp.
 //
 // Two builds (never shipped, never loaded by the product path):
-//   * default (tests/test_sanitize.py): kernel launchers enqueue nothing; engine.cpp's argument
+//   * default (tests/test_sanitize.py): the kernel launchers compute nothing but read their inputs
+//     and write patterns over their outputs (see "kernel launchers" below); engine.cpp's argument
 //     validation, staging and error paths run under ASan + UBSan.
 //   * -DMPX_STUB_ORACLE=1 (tests/test_dist.py, libmpx_stub.so): the group-step launchers run the
 //     CPU oracle (oracle/oracle.cpp, linked into the stub) and the RCCL calls really reduce across
@@ -233,20 +234,90 @@ ncclResult_t ncclGetVersion(int* v) { *v = 1; return ncclSuccess; }
 extern "C" int orc_group_step(int N, int mode, const mpx_group_batch* b, uint32_t kv_per_group);
 #endif
 
+// ---- kernel launchers ---------------------------------------------------------------------------
+// No kernel runs here, but every launcher touches memory as its kernel's contract says, so that
+// engine.cpp's staging is exercised (under ASan a slot that is too small faults in here, and
+// abi_driver.cpp checks what comes back):
+//   * it reads every byte of every input array;
+//   * an in/out array that is not state (scalars, watermarks, ret / conf_prev of the group step)
+//     comes back with every byte inverted, which shows the copy in, the copy out and the extent;
+//   * it fills output k (k = 0, 1, ... over the launcher's pure outputs, in signature order) with
+//     the byte 0xA0 + k over exactly the extent the kernel may write; optional outputs only
+//     when given;
+//   * state passed as st_in / st_out (or *_in / *_out tables) is copied across;
+//   * scratch is filled over its whole stated size;
+//   * offsets a host form reads back to size its second copy (the log encoder's rec_off, the
+//     AcceptReply encoder's dest_off) get real values instead of a pattern.
+namespace {
+volatile uint64_t g_sink;
+void touch(const void* p, size_t bytes) {
+    uint64_t s = 0;
+    for (size_t i = 0; i < bytes; ++i) s += static_cast<const uint8_t*>(p)[i];
+    g_sink = g_sink + s;
+}
+void fill(void* p, size_t bytes, int k) {
+    if (p && bytes) memset(p, 0xA0 + k, bytes);
+}
+void flip(void* p, size_t bytes) {
+    for (size_t i = 0; i < bytes; ++i) static_cast<uint8_t*>(p)[i] ^= 0xFF;
+}
+void carry(void* out, const void* in, size_t bytes) {
+    touch(in, bytes);
+    if (bytes && out != in) memmove(out, in, bytes);
+}
+void scratch(void* p, size_t bytes) {
+    if (p && bytes) memset(p, 0xEE, bytes);
+}
+}  // namespace
+
 namespace mpx {
-hipError_t launch_accept_tally(int, const mpx_accept_reply*, uint64_t, const mpx_inst_state*,
-                               mpx_inst_state*, uint64_t, int32_t, int32_t, int32_t*, uint8_t*,
-                               unsigned long long*, uint32_t*, uint32_t*, hipStream_t) { return hipSuccess; }
-hipError_t launch_committed_prefix(const mpx_inst_state*, uint64_t, int32_t, int32_t*,
-                                   unsigned long long*, hipStream_t) { return hipSuccess; }
-hipError_t launch_prepare_classic(const mpx_prepare_reply*, uint64_t, const mpx_prep_state*,
-                                  mpx_prep_state*, uint64_t, int32_t, int32_t, int32_t*, uint8_t*,
-                                  uint32_t*, uint32_t*, hipStream_t) { return hipSuccess; }
-hipError_t launch_prepare_min(const mpx_prepare_reply_min*, uint64_t, const uint64_t*,
-                              mpx_group_prep_state*, uint64_t, int32_t, int32_t*,
-                              mpx_prepare_effect*, uint32_t*, hipStream_t) { return hipSuccess; }
-hipError_t launch_conflict_batch(const uint8_t*, const int64_t*, const uint64_t*, uint64_t,
-                                 uint8_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_accept_tally(int, const mpx_accept_reply* recs, uint64_t n,
+                               const mpx_inst_state* st_in, mpx_inst_state* st_out,
+                               uint64_t n_inst, int32_t, int32_t nrep, int32_t* scalars,
+                               uint8_t* decided, unsigned long long*, uint32_t*, uint32_t*,
+                               hipStream_t) {
+    touch(recs, n * sizeof(*recs));
+    carry(st_out, st_in, n_inst * sizeof(*st_in));
+    flip(scalars, (1 + nrep) * sizeof(int32_t));
+    fill(decided, n_inst, 0);
+    return hipSuccess;
+}
+hipError_t launch_committed_prefix(const mpx_inst_state* st, uint64_t n_inst, int32_t,
+                                   int32_t* scalars, unsigned long long*, hipStream_t) {
+    touch(st, n_inst * sizeof(*st));
+    flip(scalars, sizeof(int32_t));
+    return hipSuccess;
+}
+hipError_t launch_prepare_classic(const mpx_prepare_reply* recs, uint64_t n,
+                                  const mpx_prep_state* st_in, mpx_prep_state* st_out,
+                                  uint64_t n_inst, int32_t, int32_t, int32_t* default_ballot,
+                                  uint8_t* prepared, uint32_t*, uint32_t*, hipStream_t) {
+    touch(recs, n * sizeof(*recs));
+    carry(st_out, st_in, n_inst * sizeof(*st_in));
+    flip(default_ballot, sizeof(int32_t));
+    fill(prepared, n_inst, 0);
+    return hipSuccess;
+}
+hipError_t launch_prepare_min(const mpx_prepare_reply_min* recs, uint64_t n,
+                              const uint64_t* grp_rec_off, mpx_group_prep_state* gst,
+                              uint64_t n_groups, int32_t nrep, int32_t* peer_commits,
+                              mpx_prepare_effect* eff, uint32_t*, hipStream_t) {
+    touch(recs, n * sizeof(*recs));
+    touch(grp_rec_off, (n_groups + 1) * sizeof(uint64_t));
+    touch(gst, n_groups * sizeof(*gst));
+    flip(peer_commits, n_groups * nrep * sizeof(int32_t));
+    fill(eff, n * sizeof(*eff), 0);
+    return hipSuccess;
+}
+hipError_t launch_conflict_batch(const uint8_t* op, const int64_t* key, const uint64_t* inst_off,
+                                 uint64_t n_inst, uint8_t* out, hipStream_t) {
+    if (n_inst < 2) return hipSuccess;
+    touch(inst_off, (n_inst + 1) * sizeof(uint64_t));
+    touch(op, inst_off[n_inst]);
+    touch(key, inst_off[n_inst] * 8);
+    fill(out, n_inst - 1, 0);
+    return hipSuccess;
+}
 #if MPX_STUB_ORACLE
 bool step_one_launch_fits(int32_t, uint32_t, uint32_t) { return true; }
 // the group step through the oracle; its error codes become the kernels' error-word bits
@@ -290,10 +361,48 @@ hipError_t launch_step_totals(const mpx_group_batch* b, int64_t* totals, uint32_
 }
 #else
 bool step_one_launch_fits(int32_t, uint32_t, uint32_t) { return true; }
-hipError_t launch_group_step(int, int32_t, uint32_t, const mpx_group_batch*, uint32_t*, uint32_t*,
-                             int64_t*, uint32_t*, hipStream_t, hipEvent_t, hipEvent_t,
-                             unsigned long long*) { return hipSuccess; }
-hipError_t launch_step_totals(const mpx_group_batch*, int64_t*, uint32_t*, hipStream_t) { return hipSuccess; }
+// outputs: committed_out, executed_out, peer_out, decided, n_decided, totals (0xA0 ..); ret and
+// conf_prev are in/out (the kernels leave the values of unexecuted commands)
+hipError_t launch_group_step(int, int32_t nrep, uint32_t kv_per_group, const mpx_group_batch* b,
+                             uint32_t* worklist, uint32_t*, int64_t* totals, uint32_t*,
+                             hipStream_t, hipEvent_t, hipEvent_t, unsigned long long*) {
+    const uint64_t G = b->n_groups, ni = G * b->ipg, kv = G * kv_per_group;
+    if (!G) return hipSuccess;
+    touch(b->grp_rec_off, (G + 1) * sizeof(uint64_t));
+    touch(b->recs, b->grp_rec_off[G] * sizeof(mpx_accept_reply));
+    carry(b->st_out, b->st_in, ni * sizeof(mpx_inst_state));
+    touch(b->committed_in, G * 4);
+    touch(b->executed_in, G * 4);
+    touch(b->peer_in, G * nrep * 4);
+    touch(b->cmd_off, (ni + 1) * 4);
+    const uint64_t m = b->cmd_off[ni];
+    touch(b->op, m);
+    touch(b->key, m * 8);
+    touch(b->val, m * 8);
+    if (b->has_cmds) touch(b->has_cmds, ni);
+    flip(b->ret, m * 8);
+    if (b->conf_prev) flip(b->conf_prev, m);
+    carry(b->kv_cnt_out, b->kv_cnt_in, G * 4);
+    carry(b->kv_key_out, b->kv_key_in, kv * 8);
+    carry(b->kv_val_out, b->kv_val_in, kv * 8);
+    fill(b->committed_out, G * 4, 0);
+    fill(b->executed_out, G * 4, 1);
+    fill(b->peer_out, G * nrep * 4, 2);
+    fill(b->decided, ni, 3);
+    fill(b->n_decided, G * 4, 4);
+    fill(totals, 3 * sizeof(int64_t), 5);
+    touch(worklist, G * sizeof(uint32_t));  // (the engine keeps it zeroed and large enough)
+    return hipSuccess;
+}
+hipError_t launch_step_totals(const mpx_group_batch* b, int64_t* totals, uint32_t*, hipStream_t) {
+    const uint64_t G = b->n_groups;
+    touch(b->n_decided, G * 4);
+    touch(b->executed_in, G * 4);
+    touch(b->executed_out, G * 4);
+    if (G) touch(b->cmd_off, (G * b->ipg + 1) * 4);
+    fill(totals, 3 * sizeof(int64_t), 0);
+    return hipSuccess;
+}
 #endif
 uint64_t apply_chunk_commands(uint64_t c, uint64_t m) { return c ? c : m; }
 // the engine's pinned-staging branch for replica-sized calls (same rule as apply.hip)
@@ -302,8 +411,17 @@ bool apply_is_one_launch(const ApplyOpts& o, uint64_t m) {
 }
 uint64_t apply_work_bytes(const KvTable&, const ApplyOpts&, uint64_t m) { return 48 * m + 256; }
 uint64_t apply_reserve_bytes(const KvTable&, const ApplyOpts&, uint64_t m) { return 48 * m + 256; }
-hipError_t launch_apply(KvTable&, const uint8_t*, const int64_t*, const int64_t*, uint64_t,
-                        int64_t*, uint8_t*, const ApplyOpts&, ApplyWork&, uint32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_apply(KvTable&, const uint8_t* op, const int64_t* key, const int64_t* val,
+                        uint64_t m, int64_t* ret, uint8_t* conf, const ApplyOpts&, ApplyWork& w,
+                        uint32_t*, hipStream_t) {
+    touch(op, m);
+    touch(key, m * 8);
+    touch(val, m * 8);
+    fill(ret, m * 8, 0);
+    fill(conf, m, 1);
+    scratch(w.base, w.bytes);
+    return hipSuccess;
+}
 // the replica-batch form: nothing to compute on the stub, but the call completes (its flag)
 hipError_t launch_apply_small(KvTable&, const uint8_t*, const int64_t*, const int64_t*, uint64_t,
                               int64_t*, uint8_t*, uint32_t*, hipStream_t, uint32_t* done,
@@ -312,27 +430,115 @@ hipError_t launch_apply_small(KvTable&, const uint8_t*, const int64_t*, const in
     return hipSuccess;
 }
 hipError_t launch_kv_clear(KvTable&, hipStream_t) { return hipSuccess; }
-hipError_t launch_kv_import(KvTable&, const int64_t*, const int64_t*, uint64_t, uint32_t*,
-                            hipStream_t) { return hipSuccess; }
-hipError_t launch_kv_export(KvTable&, int64_t*, int64_t*, uint64_t, unsigned long long*,
-                            hipStream_t) { return hipSuccess; }
+hipError_t launch_kv_import(KvTable&, const int64_t* keys, const int64_t* vals, uint64_t n,
+                            uint32_t*, hipStream_t) {
+    touch(keys, n * 8);
+    touch(vals, n * 8);
+    return hipSuccess;
+}
+hipError_t launch_kv_export(KvTable&, int64_t* keys, int64_t* vals, uint64_t cap,
+                            unsigned long long*, hipStream_t) {
+    fill(keys, cap * 8, 0);
+    fill(vals, cap * 8, 1);
+    return hipSuccess;
+}
 uint64_t decode_work_bytes(uint64_t len) { return len / 8 + 256; }
-hipError_t launch_decode_peer_stream(const uint8_t*, uint64_t, mpx_accept_reply*, uint64_t,
-                                     mpx_peer_frame*, uint64_t, mpx_decode_result*, void*,
-                                     uint64_t, hipStream_t) { return hipSuccess; }
+hipError_t launch_decode_peer_stream(const uint8_t* buf, uint64_t len, mpx_accept_reply* ar,
+                                     uint64_t ar_cap, mpx_peer_frame* oth, uint64_t oth_cap,
+                                     mpx_decode_result* res, void* work, uint64_t work_bytes,
+                                     hipStream_t) {
+    touch(buf, len);
+    fill(ar, ar_cap * sizeof(*ar), 0);
+    fill(oth, oth_cap * sizeof(*oth), 1);
+    fill(res, sizeof(*res), 2);  // (counts past every capacity: the host form copies the caps)
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
 uint64_t stream_work_bytes(uint64_t len) { return len + 256; }
-hipError_t launch_decode_stream(int, int, const uint8_t*, uint64_t, uint64_t, const StreamOuts&,
-                                mpx_stream_result*, void*, uint64_t, hipStream_t) { return hipSuccess; }
+hipError_t launch_decode_stream(int proto, int, const uint8_t* buf, uint64_t len, uint64_t,
+                                const StreamOuts& o, mpx_stream_result* res, void* work,
+                                uint64_t work_bytes, hipStream_t) {
+    touch(buf, len);
+    touch(res, sizeof(*res));  // (the counts carry over from window to window)
+    fill(o.ar, o.ar_cap * sizeof(*o.ar), 0);
+    fill(o.prep, o.prep_cap * (proto == MPX_MODE_MIN ? sizeof(mpx_prepare_reply_min)
+                                                     : sizeof(mpx_prepare_reply)), 1);
+    fill(o.var, o.var_cap * sizeof(*o.var), 2);
+    fill(o.oth, o.oth_cap * sizeof(*o.oth), 3);
+    fill(res, sizeof(*res), 4);  // (no stop reason the host loop continues on)
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
 uint64_t fanout_work_bytes(uint64_t n) { return 8 * n + 256; }
-hipError_t launch_encode_replies(const mpx_reply_rec*, uint64_t, uint32_t, uint8_t, int32_t,
-                                 uint8_t*, uint64_t*, void*, uint64_t, uint32_t*, hipStream_t) { return hipSuccess; }
+hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t n_clients, uint8_t,
+                                 int32_t, uint8_t* out, uint64_t* client_off, void* work,
+                                 uint64_t work_bytes, uint32_t*, hipStream_t) {
+    touch(recs, n * sizeof(*recs));
+    fill(out, n * MPX_PROPOSE_REPLY_BYTES, 0);
+    fill(client_off, ((uint64_t)n_clients + 1) * sizeof(uint64_t), 1);
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
+hipError_t launch_accept_handle(int, const mpx_accept_msg* msgs, uint64_t n,
+                                const mpx_acceptor_state* st_in, mpx_acceptor_state* st_out,
+                                uint64_t n_inst, int32_t, const mpx_acceptor_group* groups,
+                                uint64_t n_groups, uint32_t, int32_t, mpx_accept_reply* replies,
+                                int32_t* reply_to, uint8_t* effect, uint32_t*, hipStream_t) {
+    touch(msgs, n * sizeof(*msgs));
+    carry(st_out, st_in, n_inst * sizeof(*st_in));
+    touch(groups, n_groups * sizeof(*groups));
+    fill(replies, n * sizeof(*replies), 0);
+    fill(reply_to, n * sizeof(int32_t), 1);
+    fill(effect, n, 2);
+    return hipSuccess;
+}
+uint64_t accept_replies_work_bytes(uint64_t n) { return 4 * n + 256; }
+// dest_off: n frames split evenly over the destinations
+hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replies,
+                                        const int32_t* reply_to, uint64_t n, uint32_t n_dest,
+                                        uint8_t* out, uint64_t* dest_off, void* work,
+                                        uint64_t work_bytes, uint32_t*, hipStream_t) {
+    const uint64_t frame =
+        mode == MPX_MODE_MIN ? MPX_ACCEPT_REPLY_FRAME_MIN : MPX_ACCEPT_REPLY_FRAME_CLASSIC;
+    touch(replies, n * sizeof(*replies));
+    touch(reply_to, n * sizeof(int32_t));
+    for (uint64_t d = 0; d <= n_dest; ++d) dest_off[d] = n * d / n_dest * frame;
+    fill(out, n * frame, 0);
+    if (n) scratch(work, work_bytes);
+    return hipSuccess;
+}
 uint64_t logenc_work_bytes(uint64_t n, uint64_t) { return 8 * n + 256; }
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m) { return 18 * n + 17 * m; }
-hipError_t launch_encode_log(int, const mpx_log_rec*, uint64_t, const uint64_t*, const uint8_t*,
-                             const int64_t*, const int64_t*, uint64_t, uint8_t*, uint64_t*, void*,
-                             uint64_t, hipStream_t) { return hipSuccess; }
-hipError_t launch_replay_durable(const uint8_t*, uint64_t, int32_t, int32_t, mpx_log_rec*,
-                                 uint8_t*, int64_t*, int64_t*, int32_t*, int32_t*, uint32_t*,
-                                 void*, uint64_t, hipStream_t) { return hipSuccess; }
+// rec_off: 18 bytes per record and 17 per command, as the bound above
+hipError_t launch_encode_log(int, const mpx_log_rec* recs, uint64_t n, const uint64_t* cmd_off,
+                             const uint8_t* op, const int64_t* key, const int64_t* val, uint64_t m,
+                             uint8_t* out, uint64_t* rec_off, void* work, uint64_t work_bytes,
+                             hipStream_t) {
+    touch(recs, n * sizeof(*recs));
+    if (n) touch(cmd_off, (n + 1) * sizeof(uint64_t));
+    touch(op, m);
+    touch(key, m * 8);
+    touch(val, m * 8);
+    rec_off[0] = 0;
+    for (uint64_t i = 1; i <= n; ++i) rec_off[i] = 18 * i + 17 * (cmd_off[i] - cmd_off[0]);
+    fill(out, rec_off[n], 0);
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
+// last_rec and scalars are in/out
+hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_cap, int32_t,
+                                 mpx_log_rec* recs, uint8_t* op, int64_t* key, int64_t* val,
+                                 int32_t* last_rec, int32_t* scalars, uint32_t*, void* work,
+                                 uint64_t work_bytes, hipStream_t) {
+    touch(log, n * MPX_DURABLE_REC_BYTES);
+    flip(last_rec, (uint64_t)inst_cap * sizeof(int32_t));
+    flip(scalars, 2 * sizeof(int32_t));
+    fill(recs, n * sizeof(*recs), 0);
+    fill(op, n, 1);
+    fill(key, n * 8, 2);
+    fill(val, n * 8, 3);
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
 uint64_t replay_work_bytes(uint64_t n, int32_t) { return 16 * n + 256; }
 }  // namespace mpx

@@ -127,7 +127,8 @@ def test_new_entry_points_reject_a_null_engine():
 
 
 def test_stub_build_exports_the_entry_points_without_the_kernels(stub_lib):
-    """the CPU build of engine.cpp (no acceptor launchers linked) still loads and exports them"""
+    """the CPU build of engine.cpp (the stub's stand-ins for the acceptor launchers linked, no
+    weak symbol left) loads and exports them"""
     lib = C.CDLL(stub_lib)
     for name in ("mpx_accept_handle", "mpx_accept_handle_dev", "mpx_encode_accept_replies",
                  "mpx_encode_accept_replies_reserve", "mpx_encode_accept_replies_dev"):

@@ -1058,3 +1058,49 @@ def test_group_step_graph_replay(mk_engine):
         finally:
             e.graph_destroy(g)
             e.stream_destroy(s)
+
+
+# ---- the host forms' shared staging arena ---------------------------------------------------------
+def test_host_forms_share_one_staging_arena(mk_engine):
+    """Host forms of different families back to back on one handle: every one lays its arrays out
+    afresh in the handle's one staging arena, which regrows at the 4096-instance tally. A pointer
+    kept across that grow, or two slots that overlap, would change a result: all are bit-exact
+    against the oracle, and the first call repeated at the end gives what it gave at the start.
+    apply_path SORTED: a 300-command mpx_apply stages through the arena too."""
+    K = 64
+    e = mk_engine(5, R.MODE_MIN, kv_per_group=K, apply_path=R.APPLY_SORTED)
+    o = Oracle(5, R.MODE_MIN, kv_per_group=K)
+    rng = np.random.default_rng(2024)
+
+    def tally(rec, st):
+        pc0 = np.arange(5, dtype=np.int32)
+        got = e.accept_tally(rec, st, 0, -1, pc0)
+        want = o.accept_tally(rec, st, 0, -1, pc0)
+        eq_struct(got[0], want[0])
+        assert got[1] == want[1] and np.array_equal(got[2], want[2])
+        assert np.array_equal(got[3], want[3])
+        return got
+
+    rec64, st64 = synth.accept_replies(64, 5, 0.7, seed=7)
+    first = tally(rec64, st64)
+
+    op, key, val = gen_cases.commands_mixed(rng, 300, 16, neg_keys=False)
+    gr, gc = e.apply(op, key, val)
+    wr, wc = o.apply(op, key, val)
+    assert np.array_equal(gr, wr) and np.array_equal(gc, wc)
+
+    G, ipg = 4, 8
+    b = synth.group_batch(G, ipg, 5, 2, K, seed=8)
+    _cmp_group(e.group_step(b), o.group_step(b), G, K)
+
+    tally(*synth.accept_replies(4096, 5, 0.7, seed=9))  # larger than all before: the arena regrows
+
+    sizes = rng.integers(0, 7, 8)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    cop, ckey, _ = gen_cases.commands_mixed(rng, int(off[-1]), 6, neg_keys=False)
+    assert np.array_equal(e.conflict_batch(cop, ckey, off), o.conflict_batch(cop, ckey, off))
+
+    again = tally(rec64, st64)
+    eq_struct(again[0], first[0])
+    assert again[1] == first[1] and np.array_equal(again[2], first[2])
+    assert np.array_equal(again[3], first[3])
