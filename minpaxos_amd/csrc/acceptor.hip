@@ -89,17 +89,10 @@ __device__ __forceinline__ AhOut ah_step(int4& st, int4 m, int32_t D, int32_t se
 // 4 waves per SIMD (at most 128 VGPRs): left to itself the compiler takes 139 / 141 and runs 3.
 // Same-box A/B, alternating, 2^24 single-Accept instances: 0.246-0.248 -> 0.223-0.225 ms MIN,
 // 0.250 -> 0.232-0.233 ms CLASSIC (whose 8 bytes of scratch per lane cost less than the wave).
-// A/B builds: make variant_of FILE=acceptor DEFS=-DMPX_ACCEPT_WPE=0
-#ifndef MPX_ACCEPT_WPE
-#define MPX_ACCEPT_WPE 4
-#endif
-#if MPX_ACCEPT_WPE
-#define MPX_ACCEPT_ATTR __attribute__((amdgpu_waves_per_eu(MPX_ACCEPT_WPE, MPX_ACCEPT_WPE)))
-#else
-#define MPX_ACCEPT_ATTR
-#endif
+constexpr int kAcceptWpe = 4;
 template <int MODE>
-__global__ MPX_ACCEPT_ATTR __launch_bounds__(kTileBlock) void k_accept_handle(
+__global__ __attribute__((amdgpu_waves_per_eu(kAcceptWpe, kAcceptWpe)))
+__launch_bounds__(kTileBlock) void k_accept_handle(
     const mpx_accept_msg* __restrict__ msgs, uint64_t n, const mpx_acceptor_state* __restrict__ st_in,
     mpx_acceptor_state* __restrict__ st_out, uint64_t n_inst, int32_t base,
     const mpx_acceptor_group* __restrict__ groups, uint32_t one_group, uint32_t ipg, int32_t nrep,

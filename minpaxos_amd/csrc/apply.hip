@@ -167,18 +167,11 @@ __device__ __forceinline__ uint32_t op_class(uint8_t o) {
 // probes while other lanes insert read the key words with plain (L2-cached) loads: a slot's key
 // changes at most once per call (empty -> key), so a key read is final and only "empty" can be
 // stale - an insert then claims the slot with the CAS (which returns the true word), a probe's
-// miss is re-probed by k_kv_reprobe after the pass. MPX_INDEX_PLAIN=0: relaxed agent-scope
-// atomic loads instead (they bypass the XCD's L2).
-#ifndef MPX_INDEX_PLAIN
-#define MPX_INDEX_PLAIN 0
-#endif
+// miss is re-probed by k_kv_reprobe after the pass. The loads are relaxed agent-scope
+// atomic loads (they bypass the XCD's L2); plain loads were measured and not kept.
 __device__ __forceinline__ unsigned long long probe_load(const int64_t* p) {
-#if MPX_INDEX_PLAIN
-    return (unsigned long long)*p;
-#else
     return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 // the two probe loops resumed at slot s whose key `cur` was already loaded (k_kv_index issues
 // the first probe of several commands together)
@@ -221,10 +214,7 @@ __device__ __forceinline__ int64_t kv_probe_racy_from(const KvTable& t, int64_t 
 // insert / lookup passes left half the lanes of each wave idle). PUTs insert; the others probe
 // concurrently and append a miss to `miss` (one counter atomic per wave). Each lane takes
 // kIndexUnroll commands per round and issues their first probes together.
-#ifndef MPX_INDEX_UNROLL
-#define MPX_INDEX_UNROLL 2
-#endif
-constexpr int kIndexUnroll = MPX_INDEX_UNROLL;
+constexpr int kIndexUnroll = 2;
 __global__ __launch_bounds__(256) void k_kv_index(KvTable t, const uint8_t* __restrict__ op,
                                                   const int64_t* __restrict__ key, uint64_t m,
                                                   uint32_t* err, uint64_t* __restrict__ skey,
@@ -666,15 +656,10 @@ hipError_t launch_apply(KvTable& t, const uint8_t* op, const int64_t* key, const
 // striding over the products with an early exit on the first hit.
 // (4: the products of two 4-command instances in registers take 16 key registers, not 32, and
 // the kernel runs at higher occupancy; pairs with more commands take the wave path)
-#ifndef MPX_CONF_SMALL
-#define MPX_CONF_SMALL 4
-#endif
-constexpr int kSmall = MPX_CONF_SMALL;
+constexpr int kSmall = 4;
+static_assert(kSmall * kSmall <= 32, "small_pair_lds keeps a pair's products as bits of one u32");
 constexpr int kConfBlock = 256;
-#ifndef MPX_CONF_STAGE
-#define MPX_CONF_STAGE 1534
-#endif
-constexpr int kStage = MPX_CONF_STAGE;  // staged commands: 12 KB of keys with the slack, 8 workgroups per CU
+constexpr int kStage = 1534;  // staged commands: 12 KB of keys with the slack, 8 workgroups per CU
 constexpr int kStageKV = (kStage + 2) / 2;  // 16-byte key vectors: the range + one key of slack
 constexpr int kStageOV = (kStage + 30) / 16;  // 16-byte op vectors: the range + 15 bytes of slack
 constexpr int kKeyRounds = (kStageKV + kConfBlock - 1) / kConfBlock;

@@ -50,12 +50,6 @@
 
 namespace mpx {
 
-// diagnostic ablation of k_ap_resolve_list (variant builds only): 2 no result stores, 4 one step
-// of each list walk (uniform call, round 6: 0.95 -> 0.80 / 0.86 / 0.69 ms for 2 / 4 / 6)
-#ifndef MPX_RS_ABL
-#define MPX_RS_ABL 0
-#endif
-
 constexpr int kTL = 4096;          // commands per log tile
 constexpr int kTT = 1024;          // threads of the tile and bin workgroups
 constexpr int kTW = kTT / kWave;   // 16 waves
@@ -512,14 +506,11 @@ __global__ __launch_bounds__(256) void k_ap_scan_rows(ApGeo g, uint32_t* __restr
 }
 
 // ---- partition ----------------------------------------------------------------------------------
-// MPX_SC_LAZYV=1: with hot keys in the chunk, a command's value is loaded only once the command is
+// With hot keys in the chunk, a command's value is loaded only once the command is
 // known to be cold (after its hot-key probe, for the current tile), not prefetched for every
 // command: a skewed chunk's hot commands (~99 % under zipf) never need theirs in the scatter
 // (zipf 1.280 / 1.285 -> 1.256 / 1.246 ms per call, uniform unchanged - it has no hot keys and
 // keeps the prefetch; profiles/r05/apply/ab_lazyv_emit_persist.txt)
-#ifndef MPX_SC_LAZYV
-#define MPX_SC_LAZYV 1
-#endif
 struct ScatterLds {
     HotLds hl;
     uint32_t lstart[kMaxBins];  // bin start inside the tile image
@@ -561,7 +552,7 @@ __global__ __launch_bounds__(kTT) void k_ap_scatter(ApGeo g, const uint8_t* __re
     // this tile's commands in registers; the next tile's are loaded while this one is ranked
     uint32_t o[kTPer];  // 32-bit: byte-packed ops make the compiler wait for the prefetch early
     int64_t k[kTPer], v[kTPer];
-    const bool lazy = MPX_SC_LAZYV && nh > 1;  // (uniform over the grid)
+    const bool lazy = nh > 1;  // (uniform over the grid)
     auto load = [&](uint32_t tile, uint32_t* o_, int64_t* k_, int64_t* v_) {
 #pragma unroll
         for (int r = 0; r < kTPer; ++r) {
@@ -741,31 +732,11 @@ __device__ __forceinline__ int64_t kv_lo_hi(int lo, int hi) {
 // table of the present keys. A bucket that runs out of slots re-runs the bin in the two-pass form
 // (every PUT key inserted first; other commands on absent keys then have no PUT in the call and
 // resolve to 0 without a slot).
-#ifndef MPX_RL_PER
-#define MPX_RL_PER 2
-#endif
-// result stores: plain (default: the emit reads them back soon, through L2) or nontemporal
-#ifndef MPX_RL_NT
-#define MPX_RL_NT 0
-#endif
-// MPX_RES16=1: a command's result travels from the resolve to the emit as ONE 16-byte record
-// (ret, conf) instead of an 8-byte ret and a separate conf byte: the emit's gather of the
-// tile's ~4-record runs is then one request per run instead of two, for 7 more bytes per
-// command written and read (uniform 2.09 -> 2.07 ms per call, zipf neutral;
-// profiles/r05/apply/ab_res16.txt). OFF by default: the padding costs 0.93 GB of HBM traffic
-// per uniform call (7.40 vs 6.47 GB, 4.16 x the algorithmic bytes instead of 3.64 x) for 1 %
-#ifndef MPX_RES16
-#define MPX_RES16 0
-#endif
-// MPX_RES_IMG=1: the resolve stores each result at its record's IMAGE position (the tile's own
-// slots, the runs of the records' gather), so the emit reads its tile's results in one
-// contiguous run instead of gathering them run by run from partition order
-#ifndef MPX_RL_XCD
-#define MPX_RL_XCD 1
-#endif
-#ifndef MPX_RES_IMG
-#define MPX_RES_IMG 1
-#endif
+// Result stores are plain: the emit reads them back soon, through L2. The resolve stores each
+// result (an 8-byte ret and a conf byte) at its record's IMAGE position (the tile's own slots, the
+// runs of the records' gather), so the emit reads its tile's results in one contiguous run instead
+// of gathering them run by run from partition order. One 16-byte (ret, conf) record per result
+// was 1 % faster on uniform for 0.93 GB more HBM traffic per call (profiles/r05/apply/ab_res16.txt).
 // diagnostic build: wave 0's clock per phase of k_ap_resolve_list, printed by bin 0
 #ifndef MPX_RL_STAMP
 #define MPX_RL_STAMP 0
@@ -782,7 +753,8 @@ __device__ __forceinline__ int64_t kv_lo_hi(int lo, int hi) {
 #endif
 constexpr int kLT = 1024;                 // threads of the list-resolve workgroup
 constexpr int kLW = kLT / kWave;
-constexpr int kLPer = MPX_RL_PER;         // records per thread and batch
+// (3 spilled a VGPR in the hot loop, 2.13 vs 2.09-2.11 ms uniform; 1 gave 1.31-1.34 vs 1.28-1.29 zipf)
+constexpr int kLPer = 2;                  // records per thread and batch
 constexpr int kLB = kLT * kLPer;          // records per batch
 constexpr int kLSlots = kMaxBPB * kSB;    // table slots of a bin
 constexpr uint32_t kLIdx = 13;            // bits of 1 + a batch index
@@ -845,7 +817,7 @@ __global__ __launch_bounds__(kLT) void k_ap_resolve_list(ApGeo g, KvTable t,
     // XCD-contiguous bins (workgroup b runs on XCD b % 8): the bins one XCD resolves side by side
     // are neighbours, so their runs of a tile image - adjacent in it - meet in that XCD's L2: the
     // gathers' shared lines and the results' partial lines are merged there, not in HBM
-    const uint32_t bin = MPX_RL_XCD ? xcd_tile(g.nbin) : blockIdx.x;
+    const uint32_t bin = xcd_tile(g.nbin);
     const uint32_t nslot = bpb * kSB;
     const uint32_t nsub = 1u << g.lgsub;
     const uint32_t ep = t.epoch[0];
@@ -1258,7 +1230,6 @@ __global__ __launch_bounds__(kLT) void k_ap_resolve_list(ApGeo g, KvTable t,
                         }
                         j1[hh] = lk[hh] & 0x7FFFu;
                     }
-                    if (MPX_RS_ABL & 4) break;  // (diagnostic: one step of each list)
                 }
                 int64_t lpv[kLPer];
 #pragma unroll
@@ -1293,24 +1264,9 @@ __global__ __launch_bounds__(kLT) void k_ap_resolve_list(ApGeo g, KvTable t,
                     // (every record stores, those not of this pass to the spare slot past the chunk:
                     // a fixed count, so the wait for the next batch, loaded before these stores,
                     // does not wait for them)
-#if MPX_RES_IMG
                     const uint32_t dst = (cl[hh] & 1u) ? cur[hh] : spare;
-#else
-                    const uint32_t dst = (cl[hh] & 1u) ? base + i : spare;
-#endif
-                    if (!(MPX_RS_ABL & 2)) {
-#if MPX_RES16
-                        reinterpret_cast<int4*>(r_ret)[dst] =
-                            make_int4((int)(uint32_t)ret, (int)(uint32_t)((uint64_t)ret >> 32),
-                                      conf ? 1 : 0, 0);
-#elif MPX_RL_NT
-                        st_stream(r_ret + dst, ret);
-                        st_stream(r_conf + dst, (uint8_t)(conf ? 1 : 0));
-#else
-                        r_ret[dst] = ret;
-                        r_conf[dst] = conf ? 1 : 0;
-#endif
-                    }
+                    r_ret[dst] = ret;
+                    r_conf[dst] = conf ? 1 : 0;
                 }
                 // this batch's marks are read (after the last barrier): cleared for the batch after
                 // next (marked after the next barrier)
@@ -1448,8 +1404,10 @@ struct EmitLds {
     uint32_t hfl[kHMax];
     int64_t iret[kTL];     // the tile's cold results in image order (bin runs)
     uint8_t iconf[kTL];
-    uint16_t lst[kMaxBins];  // per bin: image start of the tile's run
-    uint32_t dof[kMaxBins];  //          partition start of the run - image start
+    // unused since the partition-order gather went; dropping them shrinks the kernel's LDS
+    // (78656 -> 72448 bytes), a device-code change left to a commit that measures it
+    uint16_t lst[kMaxBins];
+    uint32_t dof[kMaxBins];
     uint32_t wsum[kTW];
 };
 
@@ -1486,7 +1444,6 @@ __global__ __launch_bounds__(kTT) void k_ap_emit(ApGeo g, const uint8_t* __restr
     }
     // the cold results, lanes over the tile image: consecutive lanes read consecutive positions of
     // one bin run (the gather in command order touched one line per lane)
-#if MPX_RES_IMG
     {  // the tile's results in image order are its own slots: one contiguous run
         const uint32_t nc = tcold[tile];
         const uint64_t r0 = (uint64_t)tile * kTL;
@@ -1496,14 +1453,8 @@ __global__ __launch_bounds__(kTT) void k_ap_emit(ApGeo g, const uint8_t* __restr
         for (int u = 0; u < kTPer; ++u) {
             const uint32_t i = tid + u * kTT;
             const bool any = i - (uint32_t)l < nc;  // (wave-uniform)
-#if MPX_RES16
-            const int4 rr = any ? reinterpret_cast<const int4*>(r_ret)[r0 + i] : make_int4(0, 0, 0, 0);
-            xr[u] = kv_lo_hi(rr.x, rr.y);
-            c[u] = (uint8_t)rr.z;
-#else
             xr[u] = any ? r_ret[r0 + i] : 0;
             c[u] = any ? r_conf[r0 + i] : 0;
-#endif
         }
 #pragma unroll
         for (int u = 0; u < kTPer; ++u) {
@@ -1514,82 +1465,6 @@ __global__ __launch_bounds__(kTT) void k_ap_emit(ApGeo g, const uint8_t* __restr
             }
         }
     }
-#else
-    {
-        // the tile's run of bin b starts at partition position rows[tile][b] and ends at the next
-        // tile's start (the bin's end after the last tile); its image start is the exclusive
-        // scan of the run lengths over the bins. An image position's run: a binary search of the
-        // runs' image starts (the last one at or before it; an empty run starts where the next
-        // one does, so the search never ends on one)
-        uint32_t rof = 0, cnt = 0;
-        if ((uint32_t)tid < g.nbin) {
-            rof = rows[(uint64_t)tile * g.rowlen + tid];
-            const uint32_t nx = tile + 1 < g.tiles ? rows[(uint64_t)(tile + 1) * g.rowlen + tid]
-                                                   : bin_start[tid + 1];
-            cnt = nx - rof;
-        }
-        uint32_t x = cnt;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (l >= d) x += y;
-        }
-        if (l == kWave - 1) S.wsum[w] = x;
-        __syncthreads();
-        uint32_t wb = 0, nc = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < kTW; ++w2) {
-            const uint32_t ws = S.wsum[w2];
-            wb += w2 < w ? ws : 0u;
-            nc += ws;
-        }
-        if ((uint32_t)tid < g.nbin) {
-            const uint32_t lst = wb + x - cnt;
-            S.lst[tid] = (uint16_t)lst;
-            S.dof[tid] = rof - lst;
-        }
-        __syncthreads();
-        uint32_t lo[kTPer];
-#pragma unroll
-        for (int u = 0; u < kTPer; ++u) lo[u] = 0;
-        // (the searches side by side; a wave whose positions are all past the tile's cold
-        // commands skips them: a skewed chunk's tiles have few)
-        const uint32_t nsearch = nc > (uint32_t)(tid - l) ? (nc - (uint32_t)(tid - l) + kTT - 1) / kTT : 0u;
-        for (uint32_t half = nsearch ? g.nbin >> 1 : 0u; half; half >>= 1) {
-#pragma unroll
-            for (int u = 0; u < kTPer; ++u) {
-                if ((uint32_t)u >= nsearch) continue;  // (wave-uniform)
-                const uint32_t i = tid + u * kTT;
-                lo[u] = S.lst[lo[u] + half] <= i ? lo[u] + half : lo[u];
-            }
-        }
-        uint32_t q[kTPer];
-#pragma unroll
-        for (int u = 0; u < kTPer; ++u) q[u] = S.dof[lo[u]] + tid + u * kTT;
-        int64_t xr[kTPer];
-        uint8_t c[kTPer];
-#pragma unroll
-        for (int u = 0; u < kTPer; ++u) {
-            const uint32_t i = tid + u * kTT;
-#if MPX_RES16
-            const int4 rr = i < nc ? reinterpret_cast<const int4*>(r_ret)[q[u]] : make_int4(0, 0, 0, 0);
-            xr[u] = kv_lo_hi(rr.x, rr.y);
-            c[u] = (uint8_t)rr.z;
-#else
-            xr[u] = i < nc ? r_ret[q[u]] : 0;
-            c[u] = i < nc ? r_conf[q[u]] : 0;
-#endif
-        }
-#pragma unroll
-        for (int u = 0; u < kTPer; ++u) {
-            const uint32_t i = tid + u * kTT;
-            if (i < nc) {
-                S.iret[i] = xr[u];
-                S.iconf[i] = c[u];
-            }
-        }
-    }
-#endif
 #pragma unroll
     for (int r = 0; r < kTPer; ++r) {
         const uint32_t j = jw + r * kWave + l;
@@ -1708,10 +1583,10 @@ FastLayout fast_layout(const KvTable& t, uint64_t c) {
     L.runs = o; o += al((uint64_t)g.tiles * g.nbin * 8);
     L.ipos = o; o += al(c * 2);
     L.tcold = o; o += al((uint64_t)g.tiles * 4);
-    // results: at partition or image positions, + the spare result (see k_ap_resolve_list)
-    const uint64_t nres = (MPX_RES_IMG ? (uint64_t)g.tiles * kTL : c) + 1;
-    L.r_ret = o; o += al(nres * (MPX_RES16 ? 16 : 8));
-    L.r_conf = o; o += MPX_RES16 ? 0 : al(nres);
+    // results: at image positions, + the spare result (see k_ap_resolve_list)
+    const uint64_t nres = (uint64_t)g.tiles * kTL + 1;
+    L.r_ret = o; o += al(nres * 8);
+    L.r_conf = o; o += al(nres);
     L.hot = o; o += al(sizeof(ApHot));
     L.total = o;
     return L;
@@ -1778,7 +1653,7 @@ hipError_t launch_apply_fast(KvTable& t, const uint8_t* op, const int64_t* key, 
         k_ap_scan_rows<<<g.ng, 256, 0, stream>>>(g, rows, part, bin_start, hot);
         k_ap_runs<<<dim3((g.tiles + kRunT - 1) / kRunT, (g.nbin + kRunB - 1) / kRunB), 256, 0,
                     stream>>>(g, rows, lrow, runs);
-        const uint32_t spare = MPX_RES_IMG ? g.tiles * (uint32_t)kTL : (uint32_t)C;
+        const uint32_t spare = g.tiles * (uint32_t)kTL;
         k_ap_resolve_list<<<g.nbin, kLT, 0, stream>>>(g, t, bin_start, runs, img, r_ret, r_conf,
                                                       spare, hot, err);
         k_ap_hot_commit<<<1, kHMax, 0, stream>>>(t, val + c0, hot, err);

@@ -131,14 +131,9 @@ __device__ __forceinline__ uint32_t block_excl_sum(SmallLds& S, uint32_t v) {
 // probe[p] = slot | kMissBit (resume position) | kNoSlot; probe[kSmMax + p] = state word.
 constexpr uint32_t kMissBit = 0x80000000u;
 constexpr int kProbeBlock = 256;
-// MPX_SMALL_FOLD=1 (A/B builds): the re-probe runs at the start of the walk kernel, its
-// workgroups then meet at a grid barrier (all of them are resident: at most 16, one per CU)
-// before the walks, so a call is two launches; 0 (the default): three launches. Same-box A/B
-// (5000 / 16000 commands, events): 14.0-14.2 / 14.4-14.5 us folded vs 13.7-13.9 / 14.0-14.1 us
-// - the grid barrier costs what the launch it saves does
-#ifndef MPX_SMALL_FOLD
-#define MPX_SMALL_FOLD 0
-#endif
+// A call is three launches. Folding the re-probe into the walk kernel behind a grid barrier (two
+// launches) was measured and removed: same-box A/B (5000 / 16000 commands, events) 14.0-14.2 /
+// 14.4-14.5 us folded vs 13.7-13.9 / 14.0-14.1 us - the grid barrier costs what the launch saves
 
 // push command p onto its slot's list of this call
 __device__ __forceinline__ uint32_t call_tag(const KvTable& t) { return t.probe[kCtlOff + 1] + 1u; }
@@ -258,28 +253,6 @@ __global__ __launch_bounds__(kProbeBlock) void k_small_reprobe(KvTable t,
     reprobe_one(t, key, m, blockIdx.x * kProbeBlock + threadIdx.x);
 }
 
-// every workgroup of the grid here before any goes on (all are resident: the walk grid is at most
-// kSmMax / kSmT = 16 one-per-CU workgroups). Each thread's agent-scope stores are performed before
-// its workgroup arrives. A bounded wait: past ~0.2 s the call fails (kErrInval) instead of hanging.
-constexpr uint32_t kGridCtr = kCtlOff + 3;  // the arrivals (reset by the call's last workgroup)
-__device__ __forceinline__ void grid_barrier(const KvTable& t, uint32_t* err) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t* ctr = &t.probe[kGridCtr];
-        (void)__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t spins = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins == (1u << 22)) {
-                if (err) *(volatile uint32_t*)err |= kErrInval;
-                break;
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // ---- 3. the list walks ----------------------------------------------------------------------
 // Command p's list holds every command of the call on its key. The nearest earlier one decides
 // conf (state.Conflict: either is a PUT), the nearest earlier PUT a GET's result, and the PUT
@@ -373,7 +346,9 @@ __device__ __forceinline__ void end_of_call(const KvTable& t, uint32_t tag) {
     }
     if (threadIdx.x == 0) {
         (void)atomic_take(&t.probe[kCtlOff]);
-        (void)atomic_take(&t.probe[kGridCtr]);
+        // (the removed grid barrier's counter: nothing raises it; the reset stays until a
+        // commit that may change device code)
+        (void)atomic_take(&t.probe[kCtlOff + 3]);
         t.probe[kCtlOff + 1] = wrap ? 0u : tag;
     }
 }
@@ -485,10 +460,7 @@ __device__ void long_lists(SmallLds& S, const KvTable& t, const uint8_t* __restr
     SM_STAMP(4);
     // the shared commands' (id, position) pairs, stably by id: two 7-bit LSD passes; entry j of
     // a pass is held by thread (j / 512) * 64 + j % 64, like the positions above
-#ifndef MPX_SMALL_RANK
-#define MPX_SMALL_RANK 1
-#endif
-    if (MPX_SMALL_RANK && m2 <= (uint32_t)kSmT) {
+    if (m2 <= (uint32_t)kSmT) {
         // few shared commands (a batch over a large key space): each entry's rank is the count
         // of smaller entries (id << 14 | position is unique, so the order is stable), one pass
         // of broadcast LDS reads instead of the two radix passes' dozen barriers
@@ -666,10 +638,6 @@ __global__ __launch_bounds__(kSmT) void k_small_walk(KvTable t, const uint8_t* _
                                                      uint32_t seq, const int64_t* __restrict__ key,
                                                      uint32_t* err) {
     __shared__ SmallLds S;
-    if (MPX_SMALL_FOLD) {  // the re-probes, then every push of the call is in
-        reprobe_one(t, key, m, blockIdx.x * kSmT + threadIdx.x);
-        grid_barrier(t, err);
-    }
     {
         bool fresh, lng;
         walk_one(t, op, val, m, blockIdx.x * kSmT + threadIdx.x, ret, conf, fresh, lng);
@@ -700,20 +668,10 @@ __global__ __launch_bounds__(kSmT) void k_small_walk(KvTable t, const uint8_t* _
 // (ticket) closes the call. Table slots are shared between partitions only as probe positions in
 // a bucket: claims are device-scope CAS as in step 1, a key is probed and listed by one
 // workgroup only.
-#ifndef MPX_SMALL_PART
-#define MPX_SMALL_PART 1
-#endif
-#ifndef MPX_SMALL_PART_CMDS
-// commands per partition (the grid: the power of two >= m / this, at most kPartMax). Same-box
-// A/B, 5000 / 16000 commands: 64 -> 9.9 / 14.2 us, 128 -> 9.3-9.6 / 13.1-13.3, 256 -> 9.7-10.0 /
-// 13.7, 512 -> 10.4-10.6 / 15.2 (more partitions: fewer commands each, but every workgroup
-// loads and hashes every key)
-#define MPX_SMALL_PART_CMDS 128
-#endif
+// commands per partition (the grid: the power of two >= m / this, at most kPartMax). Same-box A/B,
+// 5000 / 16000 commands: 64 -> 9.9 / 14.2 us, 128 -> 9.3-9.6 / 13.1-13.3, 512 -> 10.4-10.6 / 15.2
+constexpr uint64_t kPartCmds = 128;
 constexpr uint32_t kPartMax = 256;  // one workgroup per CU (the LONG phase's LDS); a power of 2
-#ifndef MPX_SMALL_FAST
-#define MPX_SMALL_FAST 1  // 0 (A/B builds): every partition takes steps 1-4
-#endif
 
 // every store of the workgroup performed (list pushes, links, slots, state words), then a barrier
 __device__ __forceinline__ void wg_barrier() {
@@ -940,7 +898,7 @@ __global__ __launch_bounds__(kSmT) void k_small_part(KvTable t, const uint8_t* _
     }
     __syncthreads();
     const uint32_t no = n_own;
-    if (MPX_SMALL_FAST && no <= (uint32_t)kSmT) {
+    if (no <= (uint32_t)kSmT) {
         uint32_t fresh = 0;
         if (part_fast(*reinterpret_cast<PartFastLds*>(S.buf[0]), t, op, key, val, lst, no, ret,
                       conf, err, fresh)) {
@@ -998,10 +956,10 @@ hipError_t launch_apply_small(KvTable& t, const uint8_t* op, const int64_t* key,
                               hipStream_t stream, uint32_t* done, uint32_t seq, bool host_io) {
     if (!m) return hipSuccess;
     if (m > (uint64_t)kSmMax || t.cap >= 0x7FFFFFFEull) return hipErrorInvalidValue;
-    if (MPX_SMALL_PART && !host_io && !done) {
-        // a power of two of partitions, about MPX_SMALL_PART_CMDS commands each
+    if (!host_io && !done) {
+        // a power of two of partitions, about kPartCmds commands each
         unsigned np = 1;
-        while (np < kPartMax && (uint64_t)np * MPX_SMALL_PART_CMDS < m) np <<= 1;
+        while (np < kPartMax && np * kPartCmds < m) np <<= 1;
         k_small_part<<<np, kSmT, 0, stream>>>(t, op, key, val, (uint32_t)m, ret, conf, err);
         return hipGetLastError();
     }
@@ -1011,7 +969,7 @@ hipError_t launch_apply_small(KvTable& t, const uint8_t* op, const int64_t* key,
     const uint8_t* d_op = reinterpret_cast<const uint8_t*>(t.probe + kSmallOpOff);
     k_small_probe<<<g, kProbeBlock, 0, stream>>>(t, op, key, val, (uint32_t)m, ret, err,
                                                  done != nullptr);
-    if (!MPX_SMALL_FOLD) k_small_reprobe<<<g, kProbeBlock, 0, stream>>>(t, d_key, (uint32_t)m);
+    k_small_reprobe<<<g, kProbeBlock, 0, stream>>>(t, d_key, (uint32_t)m);
     k_small_walk<<<(unsigned)((m + kSmT - 1) / kSmT), kSmT, 0, stream>>>(
         t, d_op, d_val, (uint32_t)m, ret, conf, done, seq, d_key, err);
     return hipGetLastError();

@@ -11,65 +11,37 @@ namespace mpx {
 constexpr int kWave = 64;
 
 // Streaming-access policy of once-read inputs and once-written outputs (records, instance
-// state, commands, results): MPX_NT bit 0 = nontemporal loads, bit 1 = nontemporal stores.
-// Both together measured 3-5 % faster on the fused group step than default-policy accesses
-// (tools/ab_step.py, same process); loads alone were slower.
-#ifndef MPX_NT
-#define MPX_NT 3
-#endif
+// state, commands, results): nontemporal loads and stores. Both together measured 3-5 % faster
+// on the fused group step than default-policy accesses (same process); loads alone were slower.
 template <typename T>
 __device__ __forceinline__ T ld_stream(const T* p) {
-#if MPX_NT & 1
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 template <typename T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
-#if MPX_NT & 2
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 template <>
 __device__ __forceinline__ int4 ld_stream<int4>(const int4* p) {
-#if MPX_NT & 1
     const v4i_t x = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
     return make_int4(x.x, x.y, x.z, x.w);
-#else
-    return *p;
-#endif
 }
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 template <>
 __device__ __forceinline__ uint4 ld_stream<uint4>(const uint4* p) {
-#if MPX_NT & 1
     const v4u_t x = __builtin_nontemporal_load(reinterpret_cast<const v4u_t*>(p));
     return make_uint4(x.x, x.y, x.z, x.w);
-#else
-    return *p;
-#endif
 }
 template <>
 __device__ __forceinline__ void st_stream<uint4>(uint4* p, uint4 v) {
-#if MPX_NT & 2
     v4u_t x = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(x, reinterpret_cast<v4u_t*>(p));
-#else
-    *p = v;
-#endif
 }
 template <>
 __device__ __forceinline__ void st_stream<int4>(int4* p, int4 v) {
-#if MPX_NT & 2
     v4i_t x = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(x, reinterpret_cast<v4i_t*>(p));
-#else
-    *p = v;
-#endif
 }
 
 

@@ -29,10 +29,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-#ifndef MPX_DEC_DBL_TREE  // timing probe build: the tile tree computed twice
-#define MPX_DEC_DBL_TREE 0
-#endif
-
 namespace mpx {
 
 namespace {
@@ -230,17 +226,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_tile_maps(const uint8_t* __r
     load_chunk(buf, len, c0, wd);
     lane_map(wd, c0, len, w);
     xmap[(uint64_t)blockIdx.x * kTileLanes + threadIdx.x] = pack_exits(w);
-#ifdef MPX_DEC_ABLATE_TREE
-    if (threadIdx.x < kEntries) {  // timing ablation only: skips the tile tree (wrong results)
-        tmap[(uint64_t)blockIdx.x * kEntries + threadIdx.x] = GEntry{w[threadIdx.x] & 15u, 0, 0};
-        return;
-    }
-    return;
-#endif
-#if MPX_DEC_DBL_TREE  // timing probe: the tile tree twice (same result)
-    tile_reduce(T, w);
-    __syncthreads();
-#endif
     tile_reduce(T, w);
     if (threadIdx.x < kEntries) {
         const uint64_t x = T.m[0][threadIdx.x];
@@ -403,34 +388,24 @@ __global__ __launch_bounds__(256) void k_dec_tile_entries(const GEntry* __restri
 // The tile's bytes are staged in LDS; the true chain is walked per chunk twice (count, then
 // emit at the offsets of a block-wide exclusive scan of the counts).
 constexpr int kXPad = 20;  // bytes per exit map in LDS (17 used)
-#ifndef MPX_DEC_EMIT_REG
-#define MPX_DEC_EMIT_REG 1
-#endif
 constexpr int kDecRegAR = 10;          // a 128-byte chunk starts at most 10 AcceptReply frames
 constexpr uint32_t kDecRegCap = 1024;  // staged records per LDS pass (the tile image's space)
-// The staged tile image: 4 pad bytes after every 128-byte chunk (MPX_DEC_PAD), so the lanes -
+// The staged tile image: 4 pad bytes after every 128-byte chunk (dpofs), so the lanes -
 // one per chunk, at similar offsets - read 64 LDS banks instead of two (as the stream emit)
-#ifndef MPX_DEC_PAD
-#define MPX_DEC_PAD 1
-#endif
-__device__ __forceinline__ uint32_t dpofs(uint32_t o) { return MPX_DEC_PAD ? o + ((o >> 7) << 2) : o; }
-constexpr int kDecImg = kTileBytes + 32 + (MPX_DEC_PAD ? 4 * (kTileLanes + 1) : 0) + 16;
+__device__ __forceinline__ uint32_t dpofs(uint32_t o) { return o + ((o >> 7) << 2); }
+constexpr int kDecImg = kTileBytes + 32 + 4 * (kTileLanes + 1) + 16;
 __device__ __forceinline__ void dimg_put(uint8_t* B, int i, const uint4 v) {
-    if (MPX_DEC_PAD) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(B) + 4 * i + (i >> 3);
-        w[0] = v.x;
-        w[1] = v.y;
-        w[2] = v.z;
-        w[3] = v.w;
-    } else {
-        reinterpret_cast<uint4*>(B)[i] = v;
-    }
+    uint32_t* w = reinterpret_cast<uint32_t*>(B) + 4 * i + (i >> 3);
+    w[0] = v.x;
+    w[1] = v.y;
+    w[2] = v.z;
+    w[3] = v.w;
 }
 // 4 bytes at tile offset o from two aligned dword reads, each at its image position
 __device__ __forceinline__ int32_t lds_le32(const uint8_t* B, uint32_t o) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(B);
     const uint32_t d = o >> 2, sh = o & 3u;
-    const uint32_t d0 = MPX_DEC_PAD ? d + (d >> 5) : d, d1 = MPX_DEC_PAD ? d + 1 + ((d + 1) >> 5) : d + 1;
+    const uint32_t d0 = d + (d >> 5), d1 = d + 1 + ((d + 1) >> 5);
     const uint64_t x = ((uint64_t)w[d1] << 32) | w[d0];
     return (int32_t)(uint32_t)(x >> (8 * sh));
 }
@@ -438,21 +413,13 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
     const uint8_t* __restrict__ buf, uint64_t len, const GEntry* __restrict__ tres,
     const ulonglong2* __restrict__ xmap, mpx_accept_reply* __restrict__ ar_out, uint64_t ar_cap,
     mpx_peer_frame* __restrict__ oth_out, uint64_t oth_cap) {
-#ifndef MPX_DEC_EMIT_UNION
-#define MPX_DEC_EMIT_UNION 1
-#endif
     __shared__ uint8_t E[2 * kTileLanes - 1];  // entry per tree node (kXStop = dead)
-#if MPX_DEC_EMIT_UNION
     // the exit-map tree is dead once every chunk has its entry: the tile's bytes (loaded into
     // registers meanwhile) take its LDS, 16.7 KB per workgroup instead of 21.8 KB
     constexpr int kVec = ((kTileBytes + 32) / 16 + kTileLanes - 1) / kTileLanes;
     static_assert((2 * kTileLanes - 1) * kXPad <= kTileBytes + 32, "the tree fits the tile image");
     __shared__ __attribute__((aligned(16))) uint8_t B[kDecImg];
     uint8_t(*const X)[kXPad] = reinterpret_cast<uint8_t(*)[kXPad]>(B);
-#else
-    __shared__ uint8_t X[2 * kTileLanes - 1][kXPad];
-    __shared__ __attribute__((aligned(16))) uint8_t B[kDecImg];
-#endif
     __shared__ uint32_t wsum[kTileLanes / kWave];
     const GEntry r = tres[blockIdx.x];
     if (r.pos == kDead) return;  // uniform per block
@@ -473,7 +440,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
         }
         return v;
     };
-#if MPX_DEC_EMIT_UNION
     uint4 tv[kVec];
     if (t0 + (uint64_t)kVec * kTileLanes * 16 <= len) {
         // interior tile (block-uniform): every load in flight together, no per-load branch
@@ -489,10 +455,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
             tv[k] = i < (kTileBytes + 32) / 16 ? tile_vec(i) : make_uint4(0, 0, 0, 0);
         }
     }
-#else
-    for (int i = l; i < (kTileBytes + 32) / 16; i += kTileLanes)
-        dimg_put(B, i, tile_vec(i));
-#endif
     {
         const ulonglong2 m = xmap[(uint64_t)blockIdx.x * kTileLanes + l];
 #pragma unroll
@@ -523,7 +485,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
         __syncthreads();
     }
     const uint32_t e = E[l];
-#if MPX_DEC_EMIT_UNION
     __syncthreads();  // every lane has read its tree nodes: the tile's bytes take the tree's LDS
 #pragma unroll
     for (int k = 0; k < kVec; ++k) {
@@ -531,7 +492,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
         if (i < (kTileBytes + 32) / 16) dimg_put(B, i, tv[k]);
     }
     __syncthreads();
-#endif
     // walk 1: frames starting in this chunk on the true chain
     const uint32_t base = (uint32_t)l * kChunk;  // chunk start within the tile
     const uint64_t tl = len - t0;               // bytes of the buffer from the tile start
@@ -590,7 +550,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
     bool live = e != kXStop;
     bool is_ar;
     uint4 rec;
-#if MPX_DEC_EMIT_REG
     // the first kDecRegAR frames with their AcceptReplies in registers, then (the tile image dead)
     // through LDS, so the tile's AcceptReplies leave as coalesced runs (stream.hip k_sd_emit)
     uint32_t tot_ar = 0;
@@ -634,15 +593,6 @@ __global__ __launch_bounds__(kTileLanes) void k_dec_emit(
             if (ar0 + i < ar_cap) ar4[ar0 + i] = R[i - ph];
         __syncthreads();
     }
-#else
-    while (live) {
-        frame(p, live, is_ar, rec);
-        if (is_ar) {
-            if (ar_i < ar_cap) ar4[ar_i] = rec;
-            ++ar_i;
-        }
-    }
-#endif
 }
 
 __global__ void k_dec_empty(mpx_decode_result* res) {

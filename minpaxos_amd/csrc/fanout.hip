@@ -122,19 +122,12 @@ __global__ void k_fan_empty(uint64_t* client_off, uint32_t n_clients) {
 }
 
 // ---- counting-sort path (n_clients <= kFanMaxClients) ------------------------------------------
-#ifndef MPX_FAN_ABLATE
-#define MPX_FAN_ABLATE 0  // diagnostic builds only: 1 no write-out, 2 no encode, 8 no stores
-#endif
-#ifndef MPX_FAN_UNROLL
-#define MPX_FAN_UNROLL 2
-#endif
+constexpr int kFanUnroll = 2;                         // the write-out loop's unroll
 constexpr uint32_t kFanMaxClients = 1024;
 constexpr int kFanThreads = 512;
 constexpr int kFanWaves = kFanThreads / kWave;        // 8
-#ifndef MPX_FAN_PER
-#define MPX_FAN_PER 8
-#endif
-constexpr int kFanPer = MPX_FAN_PER;                  // replies per lane per tile
+// (2, 1024-reply tiles at two workgroups per CU: 1.89 -> 2.30 ms, the runs per client halve)
+constexpr int kFanPer = 8;                            // replies per lane per tile
 constexpr int kFanSeg = kFanPer * kWave;              // 512 replies per wave segment
 constexpr int kFanTile = kFanSeg * kFanWaves;         // 4096 replies per tile
 constexpr uint32_t kFanMaxSlices = 1024;              // workgroups (client-major histogram columns)
@@ -326,7 +319,6 @@ __global__ __launch_bounds__(kFanThreads) void k_fan_scatter(
             const uint32_t pos = tstart[cl[k]] + wcnt[w][cl[k]] + lr[k];
             sc[pos] = (uint16_t)cl[k];
             if (pos == tstart[cl[k]]) carry_in[cl[k]] = carry[cl[k]];  // before any update
-            if (MPX_FAN_ABLATE & 2) continue;
             // OK u8, CommandId i32, Value i64, Timestamp i64, Leader i32 (little endian)
             const uint32_t cid = (uint32_t)rec[k].command_id, ld = (uint32_t)leader;
             const uint64_t v = (uint64_t)rec[k].value, ts = (uint64_t)rec[k].timestamp;
@@ -345,8 +337,8 @@ __global__ __launch_bounds__(kFanThreads) void k_fan_scatter(
         // run); the dword running past the end of the client's run goes to the carry, and the
         // first reply of a run completes the dword the carry started (or, at the slice's start,
         // stores its head bytes one by one)
-#pragma unroll MPX_FAN_UNROLL
-        for (uint32_t s = t; s < ((MPX_FAN_ABLATE & 1) ? 0u : nt); s += kFanThreads) {
+#pragma unroll kFanUnroll
+        for (uint32_t s = t; s < nt; s += kFanThreads) {
             const uint32_t c = sc[s];
             const uint32_t S = tstart[c];                        // run's first image slot
             const uint64_t d = ((uint64_t)base[c] + (s - S)) * kRecBytes;  // output offset
@@ -377,7 +369,7 @@ __global__ __launch_bounds__(kFanThreads) void k_fan_scatter(
                 if (o >= (uint32_t)kRecBytes) break;
                 const uint32_t v = __builtin_amdgcn_alignbyte(B[q + 1], B[q], head);
                 if (o + 4 <= rem) {
-                    if (!(MPX_FAN_ABLATE & 8)) *reinterpret_cast<uint32_t*>(od + o) = v;
+                    *reinterpret_cast<uint32_t*>(od + o) = v;
                 } else if (o < rem) {  // the run's last reply: its partial dword waits
                     const uint32_t nb = rem - o;
                     carry[c] = 0x80000000u | (v & ((1u << (8 * nb)) - 1u));

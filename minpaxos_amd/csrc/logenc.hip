@@ -28,10 +28,7 @@ namespace {
 constexpr int kLogBlock = 256;
 // output window of one emit block: kLogWindowVec 16-byte vectors per thread (8 KB: 4 KB
 // windows measured 14% slower, 16 KB ones 13% slower at 3 workgroups per CU)
-#ifndef MPX_LOG_WINDOW_VEC
-#define MPX_LOG_WINDOW_VEC 2
-#endif
-constexpr int kLogWindowVec = MPX_LOG_WINDOW_VEC;
+constexpr int kLogWindowVec = 2;
 constexpr int kLogBlockBytes = kLogBlock * 16 * kLogWindowVec;
 // the fewest bytes a record can take (catch-up: 8 + a 1-byte varint; durable: 12)
 constexpr int kLogMinRec = 9;

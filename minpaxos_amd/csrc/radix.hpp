@@ -27,9 +27,6 @@ constexpr int kRsRounds = 16;
 constexpr int kRsWaveItems = kWave * kRsRounds;    // 1024
 constexpr int kRsTile = kRsWaveItems * kRsWaves;   // 4096
 constexpr int kRsDigits = 256;
-#ifndef MPX_RS_LDS  // the scatter's tile digit-sorted in LDS before the stores (A/B: 0)
-#define MPX_RS_LDS 1
-#endif
 
 struct RsNoValue {};
 
@@ -65,12 +62,10 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const K* __restrict__ kin, 
     constexpr bool kVals = !__is_same(V, RsNoValue);
     __shared__ uint32_t cnt[kRsWaves][kRsDigits];
     __shared__ uint32_t base[kRsDigits];
-#if MPX_RS_LDS
     __shared__ uint32_t tst[kRsDigits];  // the digits' first positions in the sorted tile
     __shared__ uint32_t wtot[kRsWaves];
     __shared__ K sk[kRsTile];
     __shared__ typename std::conditional<kVals, V, char>::type sv[kVals ? kRsTile : 1];
-#endif
     const int t = threadIdx.x, l = lane_id(), w = t / kWave;
     const uint64_t below = lanes_below(l);
 #pragma unroll
@@ -114,7 +109,6 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const K* __restrict__ kin, 
         }
         tot_d = p;
     }
-#if MPX_RS_LDS
     // the tile digit-sorted in LDS first, then stored in that order: consecutive threads write
     // consecutive positions of a digit's run (a tile holds ~16 elements per digit) instead of
     // each wave instruction landing in up to 64 runs
@@ -152,18 +146,6 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const K* __restrict__ kin, 
         kout[dst] = kk;
         if constexpr (kVals) vout[dst] = sv[i];
     }
-#else
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kRsRounds; ++r) {
-        const uint64_t i = w0 + (uint64_t)r * kWave + l;
-        if (i >= n) continue;
-        const uint32_t d = rs_digit(k[r], sh, mask);
-        const uint64_t dst = (uint64_t)base[d] + cnt[w][d] + rk[r];
-        kout[dst] = k[r];
-        if constexpr (kVals) vout[dst] = v[r];
-    }
-#endif
 }
 
 struct RsHistIn {

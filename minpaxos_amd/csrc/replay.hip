@@ -9,47 +9,31 @@
 //   instanceSpace[instNo] = {ballot, status, {0,0,0,nil}, [command]}               (:153-157)
 // The two watermarks are running maxima, so they are order-free; the last record naming an
 // instance wins its slot, so the slot keeps the HIGHEST record index.
-// The slot maximum, binned (the default when the engine holds the call's scratch,
-// replay_work_bytes; instance spaces up to kRbMaxCap slots): 2^24 random device-scope atomics
-// are request-bound on this chip (0.45 ms of the 0.69 ms call, round 3), so the slots are
-// maximised in LDS instead (round 5's form, MPX_REPLAY_SORTCHUNK=0):
-//   k_replay_durable  writes pair[i] = (rec_base + i) << 32 | instNo, coalesced (8 B / record)
-//   k_rb_count        a workgroup per chunk of kRbChunk pairs: LDS histogram of the bins
-//                     (kRbSlots = 32768 instance slots each) into hist[bin][chunk], bin-major
-//   scan              scan.hpp over the bins x chunks counts (+1: the total)
-//   k_rb_scatter      the chunk's pairs sorted by bin in LDS, then stored as the bins' runs
-//                     (order inside a bin is free: a maximum does not depend on it)
-//   k_rb_max          a workgroup per bin: the bin's slice of last_rec into LDS, one LDS
-//                     atomicMax per pair, the slice written back
-// 8 B x 4 of pair traffic per record + the slots read and written once, all coalesced.
-// MPX_REPLAY_SORTCHUNK=1 (round 6, the default) drops the count, scan and scatter passes:
+// The slot maximum, binned (when the engine holds the call's scratch, replay_work_bytes;
+// instance spaces up to kRbMaxCap slots): 2^24 random device-scope atomics are request-bound on
+// this chip (0.45 ms of the 0.69 ms call, round 3), so the slots are maximised in LDS instead:
 //   k_replay_durable  writes the record's instNo (4 B; the record index is its position)
-//   k_rb_sort         a workgroup per chunk: the chunk's instNos sorted by bin in LDS and written
-//                     back packed (chunk-local record index << 15 | slot in bin, 4 bytes) into
-//                     the chunk's own range, with each bin's start in the chunk (run starts,
-//                     chunks x (bins + 1)) - no global histogram or scan needed
-//   k_rb_max_runs     a workgroup per bin: its run in every chunk (8 lanes per run), one LDS
-//                     atomicMax per pair as before
-// 4 B written + 4 B read + 4 B written + 4 B read per record.
-// Without the scratch (or past kRbMaxCap slots), one atomicMax per record:
-// The slot maximum without a device-scope atomic per record (MPX_REPLAY_ATOMIC=0, A/B):
-//   pass 1 (k_replay_durable) raises a slot with a plain load + store when its record index is
-//          higher: racing records of one instance may leave a lower index, never a value below
-//          the slot's value at call start (memory holds it when the kernel begins);
-//   pass 2 (k_replay_fix) re-reads every record's instNo from the SoA output and lifts a slot
-//          that still holds a lower index with atomicMax - only where records of one instance
-//          raced, so (almost) no atomics.
-// MPX_REPLAY_ATOMIC=1 keeps the single pass with one atomicMax per record (A/B builds).
+//   k_rb_sort         a workgroup per chunk: the chunk's instNos sorted by bin (kRbSlots = 32768
+//                     instance slots each) in LDS and written back packed (chunk-local record
+//                     index << 15 | slot in bin, 4 bytes) into the chunk's own range, with each
+//                     bin's start in the chunk (run starts, chunks x (bins + 1)) - no global
+//                     histogram or scan needed
+//   k_rb_max_runs     a workgroup per bin: the bin's slice of last_rec into LDS, its run in every
+//                     chunk (8 lanes per run), one LDS atomicMax per pair, the slice written back
+// 4 B written + 4 B read + 4 B written + 4 B read per record + the slots read and written once,
+// all coalesced. (Round 5's form - 8-byte pairs, a global histogram, scan and scatter - moved
+// four times the pair traffic)
+// Without the scratch (or past kRbMaxCap slots), one device-scope atomicMax per record. (A
+// plain load + store pass with an atomic fix-up pass behind it was measured and not kept.)
 //
 // Layout: 256-record tiles (7424 bytes = 464 x 16 B, so every tile starts
 // 16-byte aligned when the log does); the tile is staged into LDS with 16-byte loads and each lane
 // cuts its record out of LDS, then writes the SoA outputs coalesced (16-byte mpx_log_rec, op,
 // key, val); a grid of 8 workgroups per CU walks the tiles, and each workgroup's max-reductions
 // feed one atomicMax per watermark. HBM-bound:
-// 29 B in + 33 B out + one 4-byte slot update per record (+ pass 2's 16-byte re-read).
+// 29 B in + 33 B out + one 4-byte slot update per record.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "scan.hpp"
 
 namespace mpx {
 
@@ -59,9 +43,6 @@ constexpr int kRecBytes = MPX_DURABLE_REC_BYTES;               // 12 + 17
 constexpr int kTileBytes = kReplayBlock * kRecBytes;           // 7424
 constexpr int kTileVec = kTileBytes / 16;                      // 464
 constexpr uint64_t kReplayGrid = 256 * 8;  // 256 CUs x 8 workgroups
-#ifndef MPX_REPLAY_ATOMIC
-#define MPX_REPLAY_ATOMIC 1
-#endif
 static_assert(kTileBytes % 16 == 0, "tile must be a whole number of 16-byte vectors");
 constexpr int kVecPer = (kTileVec + kReplayBlock - 1) / kReplayBlock;  // vectors per thread
 
@@ -76,18 +57,14 @@ __device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
 
 constexpr int kRbLg = 15;
 constexpr uint32_t kRbSlots = 1u << kRbLg;      // instance slots per bin (128 KB of LDS)
-constexpr uint32_t kRbMaxBins = 1024;           // the count / scatter LDS tables (4 KB)
+constexpr uint32_t kRbMaxBins = 1024;           // the sort's LDS table of bin counts (4 KB)
 constexpr int64_t kRbMaxCap = (int64_t)kRbSlots * kRbMaxBins;  // 2^25 slots
 constexpr int kRbT = 1024;
 constexpr int kRbPer = 16;
-constexpr uint64_t kRbChunk = kRbPer * kRbT;    // pairs per count / scatter workgroup (128 KB)
-constexpr uint64_t kRbNone = ~0ull;             // an instNo outside [0, inst_cap): no slot
-#ifndef MPX_REPLAY_SORTCHUNK
-#define MPX_REPLAY_SORTCHUNK 1
-#endif
+constexpr uint64_t kRbChunk = kRbPer * kRbT;    // records per sort workgroup (64 KB of LDS)
 static_assert(kRbChunk <= (1u << (32 - kRbLg)), "packed pair: chunk-local index above the slot bits");
 
-// pairs: null = the atomic form
+// pairs: null = the atomic form, else 4 bytes per record (the u64 type is historical)
 __global__ __launch_bounds__(kReplayBlock) void k_replay_durable(
     const uint8_t* __restrict__ log, uint64_t n, int32_t inst_cap, int32_t rec_base,
     mpx_log_rec* __restrict__ recs,
@@ -162,20 +139,12 @@ __global__ __launch_bounds__(kReplayBlock) void k_replay_durable(
             if (st == MPX_COMMITTED && inst > committed) committed = inst;
             // instanceSpace[instNo] panics outside the array (Go index check)
             const bool bad = inst < 0 || inst >= inst_cap;
-            if (pairs && MPX_REPLAY_SORTCHUNK)  // the instNo alone: the record index is its place
+            if (pairs)  // the instNo alone (~0: no slot): the record index is its place
                 st_stream(reinterpret_cast<uint32_t*>(pairs) + i, bad ? ~0u : (uint32_t)inst);
-            else if (pairs)
-                st_stream(pairs + i, bad ? kRbNone
-                                         : ((uint64_t)(uint32_t)(rec_base + (int32_t)i) << 32) |
-                                               (uint32_t)inst);
             if (bad)
                 raise_err(err, kErrNil);
-            else if (pairs)
-                ;
-            else if (MPX_REPLAY_ATOMIC)
+            else if (!pairs)
                 atomicMax(last_rec + inst, rec_base + (int32_t)i);
-            else if (last_rec[inst] < rec_base + (int32_t)i)
-                last_rec[inst] = rec_base + (int32_t)i;
         }
     }
     // one atomic per workgroup and watermark, skipped when it cannot raise the running value:
@@ -196,153 +165,10 @@ __global__ __launch_bounds__(kReplayBlock) void k_replay_durable(
     }
 }
 
-// pass 2: a slot below one of its records' indices lost a race in pass 1
-__global__ __launch_bounds__(256) void k_replay_fix(const mpx_log_rec* __restrict__ recs,
-                                                    uint64_t n, int32_t inst_cap,
-                                                    int32_t rec_base,
-                                                    int32_t* __restrict__ last_rec) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int32_t inst = reinterpret_cast<const int32_t*>(recs + i)[2];  // inst_no
-        if (inst < 0 || inst >= inst_cap) continue;
-        const int32_t me = rec_base + (int32_t)i;
-        if (last_rec[inst] < me) atomicMax(last_rec + inst, me);
-    }
-}
 // ---- the binned slot maximum --------------------------------------------------------------
-__global__ __launch_bounds__(kRbT) void k_rb_count(const uint64_t* __restrict__ pairs, uint64_t n,
-                                                  uint32_t bins, uint32_t chunks,
-                                                  uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[kRbMaxBins];
-    for (uint32_t b = threadIdx.x; b < bins; b += kRbT) h[b] = 0;
-    __syncthreads();
-    const uint64_t c0 = (uint64_t)blockIdx.x * kRbChunk;
-    // all of a thread's loads in flight before its first LDS atomic (an early-exit loop waited
-    // out each load in turn)
-    uint64_t p[kRbPer];
-#pragma unroll
-    for (int k = 0; k < kRbPer; ++k) {
-        const uint64_t i = c0 + (uint64_t)(threadIdx.x + k * kRbT);
-        p[k] = i < n ? ld_stream(pairs + i) : kRbNone;
-    }
-#pragma unroll
-    for (int k = 0; k < kRbPer; ++k)
-        if (p[k] != kRbNone) atomicAdd(&h[(uint32_t)p[k] >> kRbLg], 1u);
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < bins; b += kRbT) hist[(uint64_t)b * chunks + blockIdx.x] = h[b];
-}
-
-// the chunk's pairs sorted by bin in LDS first (ranks from LDS counters, a block scan of the
-// counts), then stored in that order: consecutive lanes write consecutive positions of a bin's
-// run (~32 pairs per bin and chunk at 2^24 slots) instead of 64 random 8-byte stores per wave
-// instruction (0.30 -> see DESIGN §5)
-__global__ __launch_bounds__(kRbT) void k_rb_scatter(const uint64_t* __restrict__ pairs, uint64_t n,
-                                                    uint32_t bins, uint32_t chunks,
-                                                    const uint32_t* __restrict__ offs,
-                                                    uint64_t* __restrict__ binned) {
-    __shared__ uint64_t sp[kRbChunk];
-    __shared__ uint32_t cnt[kRbMaxBins];  // counts, then the bins' starts in sp
-    __shared__ uint32_t gof[kRbMaxBins];  // the bins' first output position for this chunk
-    __shared__ uint32_t wtot[kRbT / kWave];
-    const int t = threadIdx.x, l = lane_id(), w = t / kWave;
-    for (uint32_t b = t; b < bins; b += kRbT) {
-        cnt[b] = 0;
-        gof[b] = offs[(uint64_t)b * chunks + blockIdx.x];
-    }
-    __syncthreads();
-    const uint64_t c0 = (uint64_t)blockIdx.x * kRbChunk;
-    uint64_t p[kRbPer];
-    uint32_t rk[kRbPer];
-#pragma unroll
-    for (int k = 0; k < kRbPer; ++k) {
-        const uint64_t i = c0 + (uint64_t)(t + k * kRbT);
-        p[k] = i < n ? ld_stream(pairs + i) : kRbNone;
-    }
-#pragma unroll
-    for (int k = 0; k < kRbPer; ++k)
-        rk[k] = p[k] != kRbNone ? atomicAdd(&cnt[(uint32_t)p[k] >> kRbLg], 1u) : 0u;
-    __syncthreads();
-    // exclusive scan of the counts, one bin per thread (bins <= kRbT)
-    const uint32_t c = (uint32_t)t < bins ? cnt[t] : 0u;
-    uint32_t x = c;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (l >= d) x += y;
-    }
-    if (l == kWave - 1) wtot[w] = x;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int v = 0; v < kRbT / kWave; ++v) {
-        before += v < w ? wtot[v] : 0u;
-        total += wtot[v];
-    }
-    if ((uint32_t)t < bins) cnt[t] = before + x - c;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kRbPer; ++k)
-        if (p[k] != kRbNone) sp[cnt[(uint32_t)p[k] >> kRbLg] + rk[k]] = p[k];
-    __syncthreads();
-    for (uint32_t i = t; i < total; i += kRbT) {
-        const uint64_t q = sp[i];
-        const uint32_t b = (uint32_t)q >> kRbLg;
-        binned[gof[b] + (i - cnt[b])] = q;
-    }
-}
-
-__global__ __launch_bounds__(kRbT) void k_rb_max(const uint64_t* __restrict__ binned,
-                                                uint32_t chunks, const uint32_t* __restrict__ offs,
-                                                int32_t inst_cap, int32_t* __restrict__ last_rec) {
-    __shared__ int32_t sl[kRbSlots];
-    const uint32_t b = blockIdx.x;
-    const uint64_t s0 = (uint64_t)b * kRbSlots;
-    const uint32_t ns = (uint64_t)inst_cap - s0 < kRbSlots ? (uint32_t)((uint64_t)inst_cap - s0)
-                                                            : kRbSlots;
-    // the slice's current values, then the bin's pairs, kB loads in flight per thread at a time
-    // (load-use loops waited out each load in turn)
-    constexpr int kB = 8;
-    static_assert(kRbSlots % (kB * kRbT) == 0, "whole batches of slots");
-    for (uint32_t j0 = 0; j0 < ns; j0 += kB * kRbT) {
-        int32_t v[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-            const uint32_t j = j0 + threadIdx.x + k * kRbT;
-            v[k] = j < ns ? last_rec[s0 + j] : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-            const uint32_t j = j0 + threadIdx.x + k * kRbT;
-            if (j < ns) sl[j] = v[k];
-        }
-    }
-    // the bin's run: from its first chunk's offset to the next bin's (the total after the last)
-    const uint64_t lo = offs[(uint64_t)b * chunks], hi = offs[(uint64_t)(b + 1) * chunks];
-    __syncthreads();
-    for (uint64_t i0 = lo; i0 < hi; i0 += (uint64_t)kB * kRbT) {
-        uint64_t p[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-            const uint64_t i = i0 + threadIdx.x + (uint64_t)k * kRbT;
-            p[k] = i < hi ? ld_stream(binned + i) : kRbNone;
-        }
-#pragma unroll
-        for (int k = 0; k < kB; ++k)
-            if (p[k] != kRbNone) atomicMax(&sl[(uint32_t)p[k] & (kRbSlots - 1)], (int32_t)(p[k] >> 32));
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < ns; j += kRbT) last_rec[s0 + j] = sl[j];
-}
-
 // the chunk's instNos sorted by bin in LDS, stored packed over the chunk's own range of `packed`,
 // and the bins' starts in the chunk (rs[chunk][b], b <= bins: rs[chunk][bins] = the chunk's total)
-#ifndef MPX_RB_SORT_WPE  // k_rb_sort's waves per SIMD bound (8: two workgroups per CU)
-#define MPX_RB_SORT_WPE 0
-#endif
-__global__ __launch_bounds__(kRbT)
-#if MPX_RB_SORT_WPE
-__attribute__((amdgpu_waves_per_eu(MPX_RB_SORT_WPE)))
-#endif
-void k_rb_sort(const uint32_t* __restrict__ insts, uint64_t n,
+__global__ __launch_bounds__(kRbT) void k_rb_sort(const uint32_t* __restrict__ insts, uint64_t n,
                                                  uint32_t bins, uint32_t* __restrict__ packed,
                                                  uint32_t* __restrict__ rs) {
     __shared__ uint32_t sp[kRbChunk];
@@ -474,32 +300,16 @@ __global__ __launch_bounds__(kRbT) void k_rb_max_runs(const uint32_t* __restrict
     for (uint32_t j = threadIdx.x; j < ns; j += kRbT) last_rec[s0 + j] = sl[j];
 }
 
-// the scan of hist: bins x chunks counts, then one zero item whose prefix is the total
-struct RbHistIn {
-    const uint32_t* h;
-    uint64_t n;
-    __device__ __forceinline__ uint32_t operator()(uint64_t i) const { return i < n ? h[i] : 0u; }
-};
-struct RbHistOut {
-    uint32_t* o;
-    __device__ __forceinline__ void operator()(uint64_t i, uint32_t ex, uint32_t) const { o[i] = ex; }
-};
-
 struct RbLayout {
-    uint64_t pairs, binned, hist, offs, scan, packed, rs, total;
+    uint64_t pairs, packed, rs, total;
 };
 RbLayout rb_layout(uint64_t n, int32_t inst_cap) {
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
     const uint64_t chunks = (n + kRbChunk - 1) / kRbChunk;
     const uint64_t bins = ((uint64_t)inst_cap + kRbSlots - 1) / kRbSlots;
-    const uint64_t h = bins * chunks + 1;
     RbLayout L{};
     uint64_t o = 0;
-    L.pairs = o; o += al(n * 8);
-    L.binned = o; o += al(n * 8);
-    L.hist = o; o += al(h * 4);
-    L.offs = o; o += al(h * 4);
-    L.scan = o; o += al(scan_scratch_bytes<uint32_t>(h));
+    L.pairs = o; o += al(n * 4);  // k_replay_durable's instNos, in record order
     L.packed = o; o += al(n * 4);
     L.rs = o; o += al(chunks * (bins + 1) * 4);
     L.total = o;
@@ -532,31 +342,11 @@ hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_ca
     if (binned) {
         const uint32_t chunks = (uint32_t)((n + kRbChunk - 1) / kRbChunk);
         const uint32_t bins = (uint32_t)(((uint64_t)inst_cap + kRbSlots - 1) / kRbSlots);
-        const uint64_t h = (uint64_t)bins * chunks;
-#if MPX_REPLAY_SORTCHUNK
         uint32_t* packed = (uint32_t*)(w + L.packed);
         uint32_t* rs = (uint32_t*)(w + L.rs);
         k_rb_sort<<<chunks, kRbT, 0, stream>>>((const uint32_t*)pairs, n, bins, packed, rs);
         k_rb_max_runs<<<bins, kRbT, 0, stream>>>(packed, rs, chunks, bins, inst_cap, rec_base,
                                                  last_rec);
-        return hipGetLastError();
-#endif
-        uint32_t* hist = (uint32_t*)(w + L.hist);
-        uint32_t* offs = (uint32_t*)(w + L.offs);
-        k_rb_count<<<chunks, kRbT, 0, stream>>>(pairs, n, bins, chunks, hist);
-        const hipError_t r = device_scan(RbHistIn{hist, h}, RbHistOut{offs}, h + 1, ScanSum32{},
-                                         0u, (uint32_t*)(w + L.scan), stream);
-        if (r != hipSuccess) return r;
-        k_rb_scatter<<<chunks, kRbT, 0, stream>>>(pairs, n, bins, chunks, offs,
-                                                  (uint64_t*)(w + L.binned));
-        k_rb_max<<<bins, kRbT, 0, stream>>>((const uint64_t*)(w + L.binned), chunks, offs,
-                                            inst_cap, last_rec);
-        return hipGetLastError();
-    }
-    if (!MPX_REPLAY_ATOMIC) {
-        const uint64_t g = (n + 255) / 256;
-        hipLaunchKernelGGL(k_replay_fix, dim3((unsigned)(g < 8192 ? g : 8192)), dim3(256), 0,
-                           stream, recs, n, inst_cap, rec_base, last_rec);
     }
     return hipGetLastError();
 }

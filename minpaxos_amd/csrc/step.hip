@@ -64,19 +64,10 @@ __device__ unsigned long long mpx_wg_span[kSpanMax][2];
 #define STAMP(k)
 #define STAMP_SPAN()
 #endif
-// Diagnostic A/B builds only (make variant DEFS=-DMPX_ABLATE=bits): skip a phase of k_group_fast
-// to price it (results are wrong). 1 tally, 2 key lookup, 4 resolve scan, 8 reply ranges,
-// 16 table/state outputs, 32 every instance commits (with 1: the apply without the tally).
-#ifndef MPX_ABLATE
-#define MPX_ABLATE 0
-#endif
 
-// the fast kernel's per-chunk slot match: LDS peer masks (0) or ballots over the slot bits (1:
-// 4 KB less LDS, 7-8 workgroups per CU instead of 6, but 0.667 -> 0.755 ms per config-5 step
-// in a same-box A/B, tools/gpu_step_ab.sh: more resident groups contend for the memory system)
-#ifndef MPX_STEP_BALLOT
-#define MPX_STEP_BALLOT 0
-#endif
+// The fast kernel's per-chunk slot match uses LDS peer masks. Ballots over the slot bits took
+// 4 KB less LDS (7-8 workgroups per CU instead of 6) but 0.667 -> 0.755 ms per config-5 step
+// in a same-box A/B: more resident groups contend for the memory system.
 
 constexpr int kStepBlock = 256;
 constexpr uint32_t kLock = 0xFFFFFFFFu;
@@ -296,19 +287,14 @@ struct FastCfg {
     // the table's start values in LDS (GETs of keys present at the start read them there);
     // the 1024-key variant reads them from the input table instead: its 8 KB would hold the
     // workgroup at 3 per CU (41.7 KB), without them 4 fit (33.5 KB)
-#ifndef MPX_DVAL_LDS_MAX
-#define MPX_DVAL_LDS_MAX 512
-#endif
-    static constexpr bool kFDvalLds = TB_ <= MPX_DVAL_LDS_MAX;
+    static constexpr bool kFDvalLds = TB_ <= 512;
     static_assert(kFCmds % kFT == 0 && kFRecs % kFT == 0, "whole items per thread");
     static_assert(kFCmds / 32 <= kWave, "the new-key bitmap is scanned by one wave");
     static_assert(kWaveCmds < 2047, "kTabLp holds 1 + a wave-relative command index");
     static_assert((kFH * 2) % 16 == 0, "the wave tables are cleared by 16-byte stores");
 };
-#ifndef MPX_FASTBASE_SLOTS  // A/B builds: FastBase's key slots (512, or 384: 7 workgroups per CU)
-#define MPX_FASTBASE_SLOTS 512
-#endif
-using FastBase = FastCfg<256, 1024, 1024, 256, 9, MPX_FASTBASE_SLOTS>;  // config 5: N <= 5, keys <= 256
+// (512 key slots; 384, 7 workgroups per CU, was measured and not kept)
+using FastBase = FastCfg<256, 1024, 1024, 256, 9, 512>;  // config 5: N <= 5, keys <= 256
 using FastRecs = FastCfg<256, 2048, 1024, 256, 9>;   // N <= 9
 using FastKeys = FastCfg<256, 1024, 1024, 1024, 10>; // group tables of up to 1024 keys
 using FastWide = FastCfg<512, 2048, 2048, 512, 10>;  // 512 instances per group
@@ -355,12 +341,10 @@ struct FastLds {
             // command used the slot, whether the last one was a PUT, 1 + the last PUT relative
             // to the wave's first command (0 = none)
             uint16_t tab[kFWaves * kFH];
-#if !MPX_STEP_BALLOT
             // per wave, the chunk match: slot -> a lane of the chunk on that slot (the class),
             // class -> mask of the chunk's lanes on the slot
             uint8_t win[kFWaves * kFH];
             unsigned long long pmask[kFWaves * kWave];
-#endif
         } b;
     } u;
     unsigned long long hkey[kFH];  // slot -> key; kFreeKey = free
@@ -370,9 +354,6 @@ struct FastLds {
     uint16_t coff[kFIpg + 2];       // instance -> first command (group-relative)
     uint32_t red[1 + MPX_MAX_REPLICAS];  // 1 + instance: last crossing, last peerCommits[id] source
     uint32_t firstnil, firstbad, flags, ndec;
-#ifdef MPX_LDS_PAD
-    uint8_t lds_pad[MPX_LDS_PAD];  // A/B builds only: lowers occupancy to price it
-#endif
 };
 
 // wave-uniform maximum of a per-lane value
@@ -649,20 +630,10 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
 
     // ---- phase 2: tally, one lane per instance (uniform trip count, predicated body) ----------
     bool dec = false;
-#if MPX_ABLATE & 8
-    const uint32_t ra = (uint32_t)t * 4;
-    const bool touched = true;
-    const uint32_t rn = 4;
-#else
     const uint32_t ra = own ? S.u.a.rstart[t] : kNone16;
     const bool touched = ra != kNone16;
     const uint32_t rn = touched ? (uint32_t)S.u.a.rend[t] - ra : 0;
-#endif
-#if MPX_ABLATE & 1
-    const uint32_t rmax = 0;
-#else
     const uint32_t rmax = wave_max_u32(rn);
-#endif
     if (MODE == MPX_MODE_MIN) {
         // bareminpaxos.go:1023-1053: no status check; NACKs and ballots ignored. Replies arrive in
         // ascending instance order (anything else is MPX_E_INVAL), so the LAST assignment in array
@@ -749,9 +720,7 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
 
     // ---- watermarks and the executed range (uniform) -----------------------------------------------
     int32_t cu = cu_in;
-    if (MPX_ABLATE & 32) {
-        cu = (int32_t)ipg - 1;
-    } else if (MODE == MPX_MODE_MIN) {
+    if (MODE == MPX_MODE_MIN) {
         if (S.red[0]) cu = (int32_t)S.red[0] - 1;
     } else if (S.red[0] && (int64_t)cu_in + 1 >= 0 && (int64_t)cu_in + 1 < (int64_t)ipg) {
         cu = (int32_t)S.firstbad - 1;  // updateCommittedUpTo over the final statuses
@@ -784,13 +753,11 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         if ((kFH * 2 / 16) % kWave == 0 || l + k * kWave < kFH * 2 / 16)
             reinterpret_cast<uint4*>(T)[l + k * kWave] = make_uint4(0u, 0u, 0u, 0u);
     // volatile LDS pointers: every access below is a real ds_* instruction, in program order
-#if !MPX_STEP_BALLOT
     typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
     typedef __attribute__((address_space(3))) volatile unsigned long long lds_u64;
     lds_u8* W = (lds_u8*)(S.u.b.win + wv * kFH);
     lds_u64* PM = (lds_u64*)(S.u.b.pmask + wv * kWave);
     PM[l] = 0ull;
-#endif
     const unsigned long long lanebit = 1ull << l;
     const unsigned long long below = lanebit - 1ull;
     const uint32_t wfirst = (uint32_t)wv * kWaveCmds;  // the wave's first command
@@ -802,14 +769,10 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         const bool act = li >= x0 && li < x1;
         const unsigned long long key = (unsigned long long)ck[k];
         int kd = -1;
-#if MPX_ABLATE & 2
-        if (act) kd = (int)fhome<Cfg>(ck[k]);
-#else
         if (act && key != kFreeKey) {
             int fresh = 0;
             kd = fast_slot<Cfg>(S, key, fhome<Cfg>(ck[k]), fresh);
         }
-#endif
         ebits |= (act && kd < 0) ? kOverflow : 0u;  // table full, or the key INT64_MIN
         const bool live = act && kd >= 0;
         kid[k] = live ? kd : -1;
@@ -826,18 +789,6 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         // matter: it only names the slot's class within the chunk); every lane ORs its bit into
         // its class's mask, reads the mask back, and clears it for the next chunk
         unsigned long long peers = 0;
-#if MPX_STEP_BALLOT
-        {  // one ballot per slot bit (no LDS scratch: 4 KB less per workgroup, 7 per CU)
-            unsigned long long m = livem;
-#pragma unroll
-            for (int i = 0; i < Cfg::kFHB; ++i) {
-                const bool bit = (sl >> i) & 1u;
-                const unsigned long long bm = __ballot(bit);
-                m &= bit ? bm : ~bm;
-            }
-            peers = live ? m : 0ull;
-        }
-#else
         if (live) {
             W[sl] = (uint8_t)l;
             const uint32_t cls = W[sl];
@@ -846,7 +797,6 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
             peers = PM[cls];
             PM[cls] = 0ull;
         }
-#endif
         const unsigned long long putm = __ballot(live && isput);
         const unsigned long long lp_m = peers & below;
         const unsigned long long lput_m = lp_m & putm;
@@ -886,7 +836,7 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
     // the group stays here: the instance outputs can go now (st_out may alias st_in, so not
     // before this point)
     if (own) {
-        if (!(MPX_ABLATE & 16) && touched) st_stream(reinterpret_cast<int4*>(b.st_out) + gi0 + t, st);
+        if (touched) st_stream(reinterpret_cast<int4*>(b.st_out) + gi0 + t, st);
         if (b.decided) b.decided[gi0 + t] = dec ? 1 : 0;
     }
     STAMP(4);
@@ -950,7 +900,7 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
 #pragma unroll
     for (int k = 0; k < kFTabPer; ++k) {  // original entries stay in place
         const uint32_t e = (uint32_t)t + k * kFT;
-        if (!(MPX_ABLATE & 16) && e < kcnt) {
+        if (e < kcnt) {
             const uint32_t dl = last_put((uint32_t)tslot[k]);
             kko[e] = (int64_t)S.hkey[tslot[k]];
             kvo[e] = dl ? S.u.b.cval[dl - 1] : (Cfg::kFDvalLds ? S.dval[e] : tv[k]);
@@ -974,7 +924,7 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         const uint32_t li = cbase + k * kWave;
         const uint32_t base = (uint32_t)__shfl((int)excl, (int)(li >> 5));
         const uint32_t rank = base + __popc(S.newbits[li >> 5] & ((1u << (li & 31)) - 1u));
-        if (!(MPX_ABLATE & 16) && ((fnew >> k) & 1u) && kcnt + rank < kvpg) {
+        if (((fnew >> k) & 1u) && kcnt + rank < kvpg) {
             const uint32_t kd = (uint32_t)kid[k];
             kko[kcnt + rank] = (int64_t)S.hkey[kd];
             kvo[kcnt + rank] = S.u.b.cval[last_put(kd) - 1];
@@ -1091,9 +1041,7 @@ __device__ void group_general(GenLds& S, const mpx_group_batch& b, uint32_t g, i
     // ---- watermarks --------------------------------------------------------------------------------
     const int32_t cu_in = b.committed_in[g];
     int32_t cu = cu_in;
-    if (MPX_ABLATE & 32) {
-        cu = (int32_t)ipg - 1;
-    } else if (MODE == MPX_MODE_MIN) {
+    if (MODE == MPX_MODE_MIN) {
         if (S.red[0]) cu = (int32_t)(uint32_t)(S.red[0] & 0xffffffffull);
         if (t < nrep) {
             const unsigned long long k = S.red[1 + t];

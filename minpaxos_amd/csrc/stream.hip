@@ -28,7 +28,7 @@
 // its first 8 chunks at one entry X (or die there) - nearly every tile of a real stream - has
 // chunk entries past those 8 chunks that do not depend on its entry: the framing pass stores
 // them with group 0's 8 chunk maps as the tile's TileEnt (640 bytes) instead of its 128 chunk
-// maps (8 KB), and the count pass and the walk read that (MPX_SD_TENT).
+// maps (8 KB), and the count pass and the walk read that.
 // HBM traffic per stream byte: 1 read (maps) + 1 read (count) + 1 read (emit) + 0.04 (TileEnt
 // write and read), records written once.
 #include "common.hpp"
@@ -44,23 +44,11 @@ constexpr int kE = MPX_DECODE_WINDOW;   // entry offsets per chunk map
 constexpr int kTL = 128;                // chunks (lanes) per tile
 constexpr int kTB = kC * kTL;           // tile bytes
 constexpr int kGT = 256;                // tiles per group
-#ifndef MPX_SD_VARLDS
-#define MPX_SD_VARLDS 1
-#endif
 constexpr int kDRow = kC + 4;           // LDS row of a chunk's DP (bank-conflict padding)
 constexpr int kTEnt = 8 * kE + kTL + 16;  // a tile's TileEnt bytes (+ chunks 8..127's counts)
-#ifndef MPX_SD_WPE  // k_sd_tile_maps' waves per SIMD bound (its VGPR budget)
-#define MPX_SD_WPE 5
-#endif
-#ifndef MPX_SD_TCNT  // converged tiles: chunks 8..127 counted by the framing pass (needs TENT)
-#define MPX_SD_TCNT 1
-#endif
-#ifndef MPX_SD_TENT
-#define MPX_SD_TENT 1
-#endif
-#ifndef MPX_SD_PRMARK  // PrepareReplies marked 0x60 in the landing table: a position mask, no loads
-#define MPX_SD_PRMARK 0
-#endif
+// k_sd_tile_maps' waves per SIMD bound (95 VGPRs, no spills: 0.53-0.55 ms MIN; the default 4 took
+// 110 VGPRs and 0.56-0.60 ms)
+constexpr int kMapsWpe = 5;
 #ifndef MPX_SD_TENT_NOCONV  // test build: every tile takes the unconverged path
 #define MPX_SD_TENT_NOCONV 0
 #endif
@@ -88,13 +76,10 @@ __host__ __device__ __forceinline__ uint32_t flen(uint32_t code, int proto) {
 
 // bytes of the stream: an LDS-staged window [lo, hi) (relative positions), global otherwise
 // The staged tile image of the count and emit passes: 4 pad bytes after every 128-byte chunk
-// (MPX_SD_PAD), so the lanes - one per chunk, at similar offsets - read 64 different banks
+// (pofs), so the lanes - one per chunk, at similar offsets - read 64 different banks
 // instead of two (the emit pass's SQ pass: 72 % of its LDS cycles were bank conflicts).
-#ifndef MPX_SD_PAD
-#define MPX_SD_PAD 1
-#endif
 __host__ __device__ __forceinline__ uint32_t pofs(uint32_t o) {  // image offset of stream offset o
-    return MPX_SD_PAD ? o + ((o >> 7) << 2) : o;
+    return o + ((o >> 7) << 2);
 }
 struct Bytes {
     const uint8_t* g;
@@ -216,9 +201,9 @@ struct SParams {
 
 // ---- workspace ----------------------------------------------------------------------------
 struct Work {
-    uint8_t* cmap;             // [tiles * kTL][kE] chunk maps (MPX_SD_TENT: converged tiles skip them)
+    uint8_t* cmap;             // [tiles * kTL][kE] chunk maps (converged tiles skip them)
     uint8_t* tconv;            // [tiles][kTEnt] TileEnt: group 0's chunk maps, then [0] converged,
-                               // [1] X, [8..127] the chunk entries from X (MPX_SD_TENT)
+                               // [1] X, [8..127] the chunk entries from X
     uint8_t* tmap;             // [tiles][kE]
     uint8_t* tent;             // [tiles] true entry (kDeadE past the stop)
     uint8_t* gmap;             // [groups][kE]
@@ -345,7 +330,7 @@ __host__ __device__ __forceinline__ uint32_t var_land(const ByteAt& R, uint32_t 
 // wave took as many rounds as its busiest lane, each as long as its deepest parse (catch-up
 // logs over zero-rich payload: ~20 dependent reads). Tasks (lane << 7 | position, u16) go to
 // T[kVarTasks] (the workgroup's G, free until the DP is done); lane j parses tasks j, j + 64,
-// ... The parse reads the rows' raw bytes (MPX_SD_VARLDS, written before the landings; a chunk's
+// ... The parse reads the rows' raw bytes (written before the landings; a chunk's
 // next-chunk bytes from the next row when that is the same wave's, else through L2), so a row's
 // raw bytes must outlive every parse of the wave: the results wait in registers (a byte per
 // round) and are stored after the last round. More than kVarTasks positions (a var-dense wave)
@@ -381,7 +366,7 @@ __device__ __forceinline__ uint32_t var_wave(const SParams P, uint64_t t0, uint6
         if (ln >= (uint32_t)d) incl += t;
     }
     const uint32_t total = __shfl(incl, 63, 64);
-    const bool lds = MPX_SD_VARLDS && total <= kVarTasks;
+    const bool lds = total <= kVarTasks;
     for (uint32_t base = 0; base < total; base += kVarTasks) {
         const uint32_t n = min(total - base, kVarTasks);
         uint32_t o = incl - cnt;  // this lane's first task index
@@ -434,8 +419,7 @@ __host__ __device__ constexpr uint64_t dp_table(uint64_t lut) {
     uint64_t e = 0;
     for (int i = 0; i < 8; ++i) {
         const uint64_t fl = (lut >> (8 * i)) & 0xFFu;
-        const uint64_t vm = MPX_SD_PRMARK && i == MPX_PEER_PREPARE_REPLY - MPX_PEER_BEACON ? kVarMark | 0x20u : kVarMark;
-        e |= (fl ? fl - 1 : vm) << (8 * i);
+        e |= (fl ? fl - 1 : (uint64_t)kVarMark) << (8 * i);
     }
     return e;
 }
@@ -515,7 +499,7 @@ __device__ __forceinline__ void store_chunk_map(const Work& W, uint32_t tile, co
         dst[i] = make_uint4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
 }
 
-__global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE))) void k_sd_tile_maps(SParams P, Work W) {
+__global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(kMapsWpe))) void k_sd_tile_maps(SParams P, Work W) {
 #if MPX_SD_STAMP
     unsigned long long sd_t[8];
     sd_t[0] = clock64();
@@ -551,13 +535,11 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
             wd[i] = x;
         }
     }
-#if MPX_SD_VARLDS
     {   // the raw chunk into its row (the variable-message parse's bytes; wave-local readers)
         uint32_t* row = reinterpret_cast<uint32_t*>(D[l]);
 #pragma unroll
         for (int i = 0; i < kC / 4; ++i) row[i] = wd[i];
     }
-#endif
     const uint64_t tab = P.proto == MPX_MODE_MIN ? dp_table(kLutMin) : dp_table(kLutClassic);
     const uint32_t tab_lo = (uint32_t)tab, tab_hi = (uint32_t)(tab >> 32);
     uint32_t any_var = 0;  // bit 6 of the chunk's variable-message bytes, OR-ed
@@ -570,9 +552,6 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
     }
     SD_STAMP(1);
     uint64_t m_lo = 0, m_hi = 0;  // the chunk's variable-message positions (kept for the counts)
-#if MPX_SD_PRMARK
-    uint64_t r_lo = 0, r_hi = 0;  // its PrepareReplies' (bit 5 of the table value)
-#endif
     {
         const bool wv = __ballot(any_var != 0) != 0;  // (wave-uniform)
         uint16_t* T = reinterpret_cast<uint16_t*>(&G[0][0]) + (l >> 6) * kVarTasks;
@@ -580,19 +559,9 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
 #pragma unroll
             for (int i = 0; i < kC / 4; ++i) {
                 const uint32_t pos4 = (uint32_t)(4 * i + 1) * 0x01010101u + 0x03020100u;
-#if MPX_SD_PRMARK
-                // bit 0 of a byte: variable message, bit 4: PrepareReply; gathered to two nibbles
-                const uint32_t d = wd[i] - pos4;
-                const uint32_t z = ((d >> 6) & 0x01010101u) | ((d >> 1) & 0x10101010u);
-                const uint32_t c = (z | (z >> 7) | (z >> 14) | (z >> 21));
-                const uint64_t nib = c & 0xFu, rnib = (c >> 4) & 0xFu;
-                if (i < 16) { m_lo |= nib << (4 * i); r_lo |= rnib << (4 * i); }
-                else { m_hi |= nib << (4 * (i - 16)); r_hi |= rnib << (4 * (i - 16)); }
-#else
                 const uint32_t t = var_bits(wd[i] - pos4) >> 6;  // 0x01 per variable-message byte
                 const uint64_t nib = (uint64_t)((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu);
                 if (i < 16) m_lo |= nib << (4 * i); else m_hi |= nib << (4 * (i - 16));
-#endif
             }
         }
         const uint32_t vt = wv ? var_wave(P, t0, m_lo, m_hi, D, T) : 0u;
@@ -623,14 +592,10 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
     SD_STAMP(3);
     chunk_dp_self(wd, D[l]);
     SD_STAMP(4);
-#if !MPX_SD_TENT
-    store_chunk_map(W, blockIdx.x, D[l]);
-#endif
     __syncthreads();
     SD_STAMP(5);
     chunk_groups(&D[0][0], kDRow, G);
     __syncthreads();
-#if MPX_SD_TENT
     {   // the tile's entry table (TileEnt): whether every chain from the 64 tile entries that
         // leaves group 0 (chunks 0..7) leaves it at one entry X, and the chunk entries from X on
         // TE (the entry row, 128 bytes) and GEs (the 16 group entries) live in the rows' 4 pad
@@ -683,7 +648,6 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
             store_chunk_map(W, blockIdx.x, D[l]);
         }
     }
-#endif
     {  // the tile map: the first and second 8 group maps composed by two halves of the
        // workgroup side by side, then entry l through both
         static_assert(kTL == 2 * kE && kTL / 8 == 16, "two halves of 8 group maps");
@@ -699,7 +663,6 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
             W.tmap[(uint64_t)blockIdx.x * kE + l] =
                 (uint8_t)(y >= (uint32_t)kE ? (uint32_t)kTerm : G[1][y]);
         }
-#if MPX_SD_TENT && MPX_SD_TCNT
         // A converged tile's chunks 8..127 lie on one chain whatever the tile's entry: count
         // their frames here (the count pass then reads 8 chunks of bytes instead of 128). Each
         // lane walks its chunk from its entry through the DP's pointers (landing, or itself for a
@@ -730,11 +693,7 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
                 const bool var = ((x < 64 ? m_lo >> x : m_hi >> (x - 64)) & 1ull) != 0;
                 if (var) {
                     cnt[2]++;
-#if MPX_SD_PRMARK
-                    cnt[1] += (uint32_t)((x < 64 ? r_lo >> x : r_hi >> (x - 64)) & 1ull);
-#else
                     cnt[1] += P.buf[c0 + x] == MPX_PEER_PREPARE_REPLY ? 1u : 0u;
-#endif
                 } else {
                     cnt[len == ar_len ? 0 : 3]++;
                 }
@@ -759,7 +718,6 @@ __global__ __launch_bounds__(kTL) __attribute__((amdgpu_waves_per_eu(MPX_SD_WPE)
                 reinterpret_cast<uint32_t*>(W.tconv + (uint64_t)blockIdx.x * kTEnt + 8 * kE + kTL)[l] = x;
             }
         }
-#endif
 #if MPX_SD_STAMP
         SD_STAMP(6);
         if ((blockIdx.x & 2047) == 1025 && (l & 63) == 0)
@@ -932,7 +890,6 @@ __global__ __launch_bounds__(kParts * kE) void k_sd_walk(SParams P, Work W, uint
     __syncthreads();
     // the terminal chunk within the tile: a converged tile's TileEnt (group 0's chunk maps, then
     // the chunk entries from X), else its 128 chunk maps (8 KB) over S
-#if MPX_SD_TENT
     for (uint32_t i = t; i < (uint32_t)kTEnt / 16; i += blockDim.x)
         reinterpret_cast<uint4*>(&S[0][0])[i] =
             reinterpret_cast<const uint4*>(W.tconv + (uint64_t)ts * kTEnt)[i];
@@ -961,7 +918,6 @@ __global__ __launch_bounds__(kParts * kE) void k_sd_walk(SParams P, Work W, uint
             fk[1] = x;
         }
     } else
-#endif
     {
         for (uint32_t i = t; i < (uint32_t)kTL * kE / 16; i += blockDim.x)
             reinterpret_cast<uint4*>(&S[0][0])[i] =
@@ -1065,24 +1021,20 @@ __device__ __forceinline__ int32_t le32(const Bytes& by, uint64_t i) {
 __device__ __forceinline__ int32_t lds_le32(const uint8_t* B, uint32_t o) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(B);
     const uint32_t d = o >> 2, sh = o & 3u;
-    const uint32_t d0 = MPX_SD_PAD ? d + (d >> 5) : d, d1 = MPX_SD_PAD ? d + 1 + ((d + 1) >> 5) : d + 1;
+    const uint32_t d0 = d + (d >> 5), d1 = d + 1 + ((d + 1) >> 5);
     const uint64_t x = ((uint64_t)w[d1] << 32) | w[d0];
     return (int32_t)(uint32_t)(x >> (8 * sh));
 }
 // the image's bytes: kTB + kE stream bytes, a pad per chunk (kTL + 1 chunks started), and the
 // second dword lds_le32 may read past the last byte
-constexpr int kImg = kTB + kE + (MPX_SD_PAD ? 4 * (kTL + 1) : 0) + 16;
+constexpr int kImg = kTB + kE + 4 * (kTL + 1) + 16;
 // 16 stream bytes (piece i of the tile) into the image: a piece never crosses a chunk
 __device__ __forceinline__ void img_put(uint8_t* B, int i, const uint4 v) {
-    if (MPX_SD_PAD) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(B) + 4 * i + (i >> 3);
-        w[0] = v.x;
-        w[1] = v.y;
-        w[2] = v.z;
-        w[3] = v.w;
-    } else {
-        reinterpret_cast<uint4*>(B)[i] = v;
-    }
+    uint32_t* w = reinterpret_cast<uint32_t*>(B) + 4 * i + (i >> 3);
+    w[0] = v.x;
+    w[1] = v.y;
+    w[2] = v.z;
+    w[3] = v.w;
 }
 
 // the tile's chunk entries: the tile's true entry through its chunk maps (X, in LDS)
@@ -1108,18 +1060,6 @@ __device__ __forceinline__ void chunk_entries(uint32_t ent, uint8_t (*X)[kE], ui
         }
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ void load_chunk_maps(const Work& W, uint32_t tile, uint8_t (*X)[kE]) {
-    // the 8 KB of chunk maps: a lane's four loads in flight together, then the LDS stores
-    const uint4* src = reinterpret_cast<const uint4*>(W.cmap + (uint64_t)tile * kTL * kE);
-    constexpr int kN = kTL * kE / 16 / kTL;
-    static_assert(kTL * kE / 16 % kTL == 0, "whole vectors per lane");
-    uint4 v[kN];
-#pragma unroll
-    for (int k = 0; k < kN; ++k) v[k] = src[threadIdx.x + k * kTL];
-#pragma unroll
-    for (int k = 0; k < kN; ++k) reinterpret_cast<uint4*>(&X[0][0])[threadIdx.x + k * kTL] = v[k];
 }
 
 // frames of the lane's chunk on the true chain, by kind: AcceptReplies, PrepareReplies, variable
@@ -1204,11 +1144,7 @@ __device__ __forceinline__ void load_tile_regs(const SParams& P, uint64_t t0, ui
     }
 }
 
-#ifndef MPX_SD_COUNT_UNION
-#define MPX_SD_COUNT_UNION 1
-#endif
 __global__ __launch_bounds__(kTL) void k_sd_count(SParams P, Work W) {
-#if MPX_SD_COUNT_UNION
     // the chunk maps are dead once the chunk entries are known: the tile's bytes (loaded into
     // registers meanwhile) take their LDS, so a workgroup needs 16.5 KB instead of 24.5 KB
     // (and the group maps of an unconverged tile's chunk entries take the bytes after X)
@@ -1217,31 +1153,20 @@ __global__ __launch_bounds__(kTL) void k_sd_count(SParams P, Work W) {
     uint8_t(*const X)[kE] = reinterpret_cast<uint8_t(*)[kE]>(U);
     uint8_t(*const G)[kE] = reinterpret_cast<uint8_t(*)[kE]>(U + kTL * kE);
     static_assert(kTL * kE + kTL / 8 * kE <= kImg, "X and G fit the image");
-#else
-    __shared__ __attribute__((aligned(16))) uint8_t B[kImg];
-    __shared__ __attribute__((aligned(16))) uint8_t X[kTL][kE];
-    __shared__ uint8_t G[kTL / 8][kE];
-#endif
     __shared__ uint8_t GE[kTL / 8];
     __shared__ uint8_t En[kTL];
     __shared__ uint32_t wsum[kTL / kWave][4];
     const int l = threadIdx.x;
     const uint32_t tile = blockIdx.x;
     const uint8_t ent = W.tent[tile];
-#if MPX_SD_TENT && MPX_SD_TCNT
     const bool conv_tile = W.tconv[(uint64_t)tile * kTEnt + 8 * kE] != 0;
     const bool stop_tile = W.stop[0] / kTB == tile;
-#endif
     if (ent == kDeadE) {
         if (l < 4) W.tcnt[4 * (uint64_t)tile + l] = 0;
         return;
     }
-#if MPX_SD_TENT && MPX_SD_TCNT
     if (conv_tile && !stop_tile) return;  // k_sd_count_conv's
-#endif
     const uint64_t t0 = (uint64_t)tile * kTB;
-#if MPX_SD_COUNT_UNION
-#if MPX_SD_TENT
     // the TileEnt's loads first (needed first), then the tile's, all in flight together; a
     // converged tile (the common case) needs no chunk maps past group 0
     uint4 tev = make_uint4(0, 0, 0, 0);
@@ -1272,34 +1197,14 @@ __global__ __launch_bounds__(kTL) void k_sd_count(SParams P, Work W) {
         __syncthreads();
         chunk_entries(ent, X, G, GE, En);  // (ends with a barrier: X is dead)
     }
-#else
-    // the chunk maps' loads first (needed first), then the tile's, all in flight together
-    constexpr int kCm = kTL * kE / 16 / kTL;
-    uint4 cm[kCm];
-    const uint4* csrc = reinterpret_cast<const uint4*>(W.cmap + (uint64_t)tile * kTL * kE);
-#pragma unroll
-    for (int k = 0; k < kCm; ++k) cm[k] = csrc[l + k * kTL];
-    uint4 tv[kStageVec];
-    load_tile_regs(P, t0, tv);
-#pragma unroll
-    for (int k = 0; k < kCm; ++k) reinterpret_cast<uint4*>(&X[0][0])[l + k * kTL] = cm[k];
-    __syncthreads();
-    chunk_entries(ent, X, G, GE, En);  // (ends with a barrier: X is dead)
-#endif
 #pragma unroll
     for (int k = 0; k < kStageVec; ++k) {
         const int i = l + k * kTL;
         if (i < (kTB + kE) / 16) img_put(B, i, tv[k]);
     }
     __syncthreads();
-#else
-    stage_tile(P, t0, B);
-    load_chunk_maps(W, tile, X);
-    __syncthreads();
-    chunk_entries(ent, X, G, GE, En);
-#endif
     const uint64_t c0 = t0 + (uint64_t)l * kC;
-    const Bytes by{P.buf, B, t0, t0 + kTB + kE < P.len ? t0 + kTB + kE : P.len, MPX_SD_PAD != 0};
+    const Bytes by{P.buf, B, t0, t0 + kTB + kE < P.len ? t0 + kTB + kE : P.len, true};
     uint32_t cnt[4] = {0, 0, 0, 0};
     chunk_counts(En[l], c0, W.stop[0], (int)W.stop[2] == MPX_DECODE_LONG, P, by,
                  [&](uint64_t a) { return (uint32_t)B[pofs((uint32_t)(a - t0))]; }, cnt);
@@ -1446,9 +1351,6 @@ __global__ __launch_bounds__(kScanT) void k_sd_scan(Work W, uint32_t n_tiles) {
     if (t == 0) *W.ticket = 0;
 }
 
-#ifndef MPX_SD_EMIT_REG
-#define MPX_SD_EMIT_REG 1
-#endif
 // frames whose AcceptReplies a lane keeps in registers for the staged stores (a 128-byte chunk
 // starts at most 10 MIN AcceptReply frames; 13 would cost a wave per SIMD of occupancy, so a
 // tile with a longer chunk - CLASSIC's 10-byte frames back to back - stores directly), and the
@@ -1487,7 +1389,7 @@ __global__ __launch_bounds__(kTL) void k_sd_emit(SParams P, Work W, Outs O, uint
     const uint64_t stop = W.stop[0];
     const int why = (int)W.stop[2];
     const bool long_stop = why == MPX_DECODE_LONG;
-    const Bytes by{P.buf, B, t0, t0 + kTB + kE < P.len ? t0 + kTB + kE : P.len, MPX_SD_PAD != 0};
+    const Bytes by{P.buf, B, t0, t0 + kTB + kE < P.len ? t0 + kTB + kE : P.len, true};
     const uint64_t c0 = t0 + (uint64_t)l * kC;
     const uint32_t cnt[4] = {ci.y & 0xFFu, (ci.y >> 8) & 0xFFu, (ci.y >> 16) & 0xFFu, ci.y >> 24};
     const uint64_t lut = P.proto == MPX_MODE_MIN ? kLutMin : kLutClassic;
@@ -1617,7 +1519,6 @@ __global__ __launch_bounds__(kTL) void k_sd_emit(SParams P, Work W, Outs O, uint
     bool live = e != kDeadE;
     bool is_ar;
     uint4 rec;
-#if MPX_SD_EMIT_REG
     // the lane's first kRegAR frames with their AcceptReplies held in registers ...
     uint4 rr[kRegAR];
     uint32_t rl[kRegAR];  // tile-local index, ~0 = none
@@ -1660,15 +1561,6 @@ __global__ __launch_bounds__(kTL) void k_sd_emit(SParams P, Work W, Outs O, uint
             if (ar0 + i < O.ar_cap) ar4[ar0 + i] = R[i - ph];
         __syncthreads();
     }
-#else
-    while (live) {
-        frame(a, live, is_ar, rec);
-        if (is_ar) {
-            if (idx[0] < O.ar_cap) ar4[idx[0]] = rec;
-            ++idx[0];
-        }
-    }
-#endif
 }
 
 // an empty call ([start, len) holds no byte): END, counts unchanged
@@ -1739,9 +1631,7 @@ hipError_t launch_decode_stream(int proto, int legacy, const uint8_t* buf, uint6
     k_sd_walk<<<1, kParts * kE, 0, stream>>>(P, W, tiles, groups, res);
     k_sd_tile_entries<<<groups, kParts * kE, 0, stream>>>(W, tiles);
     k_sd_count<<<tiles, kTL, 0, stream>>>(P, W);
-#if MPX_SD_TENT && MPX_SD_TCNT
     k_sd_count_conv<<<tiles, kWave, 0, stream>>>(P, W);
-#endif
     k_sd_scan<<<(tiles + kScanT - 1) / kScanT, kScanT, 0, stream>>>(W, tiles);
     k_sd_emit<<<tiles, kTL, 0, stream>>>(P, W, O, tiles, res);
     return hipGetLastError();

@@ -25,16 +25,8 @@ namespace mpx {
 // replies are written 0 in the gap pass.
 // Control words (engine-owned, zero between calls): [0] ticket, [1..1+N) MIN keys / [1] CLASSIC
 // "some instance committed", [2] CLASSIC ~first_bad.
-#ifndef MPX_TALLY_WPE
-#define MPX_TALLY_WPE 0
-#endif
-#if MPX_TALLY_WPE
-#define MPX_TALLY_ATTR __attribute__((amdgpu_waves_per_eu(MPX_TALLY_WPE, MPX_TALLY_WPE)))
-#else
-#define MPX_TALLY_ATTR
-#endif
 template <int MODE>
-__global__ MPX_TALLY_ATTR __launch_bounds__(kTileBlock) void k_accept_tile(
+__global__ __launch_bounds__(kTileBlock) void k_accept_tile(
     const mpx_accept_reply* __restrict__ recs, uint64_t n, const mpx_inst_state* __restrict__ st_in,
     mpx_inst_state* __restrict__ st_out, uint64_t n_inst, int32_t base, int32_t half, int32_t nrep,
     int32_t* __restrict__ scalars, uint32_t* __restrict__ ctl, uint8_t* __restrict__ decided,
@@ -270,9 +262,6 @@ uint32_t resident_grid(const void* kernel, int block, uint64_t tiles) {
             // one round on the config-2 tally (same-box A/B, profiles/r03)
             const uint64_t r = 2 * (uint64_t)(nb > 0 ? nb : 1) * (uint64_t)(cus > 0 ? cus : 256);
             g = (uint32_t)(r < (uint64_t)kTileGrid ? r : kTileGrid);
-#ifdef MPX_TILE_GRID  // A/B builds: a fixed grid
-            g = MPX_TILE_GRID;
-#endif
             if (used < 16) {
                 keys[used] = kernel;
                 vals[used++] = g;

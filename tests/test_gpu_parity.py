@@ -617,7 +617,7 @@ def test_apply_small_partition_skew(mk_engine):
     rng = np.random.default_rng(99)
     e, o = mk_engine(5, R.MODE_MIN, kv_capacity=1 << 16, apply_path=R.APPLY_SMALL), \
         Oracle(5, R.MODE_MIN)
-    def lg_parts(m, per=128, cap=256):  # apply_small.hip launch_apply_small (MPX_SMALL_PART_CMDS)
+    def lg_parts(m, per=128, cap=256):  # apply_small.hip launch_apply_small (kPartCmds)
         n = 1
         while n < cap and n * per < m:
             n <<= 1

@@ -81,7 +81,7 @@ def main():
         tb = tables()
         engines.append((path, lib, h, stream, tb, batch(tb, "0", "1")))
         assert lib.mpx_group_step_dev(h, C.byref(batch(tb, "1", "0")), stream) == 0  # warm-up
-        rc = lib.mpx_synchronize(h)  # ablation builds may flag errors (their results are wrong)
+        rc = lib.mpx_synchronize(h)
         if rc:
             print(f"{os.path.basename(path)}: warm-up returned {rc}")
     times = {e[0]: [] for e in engines}

@@ -2,7 +2,7 @@
 """Per-phase time of the replica-batch apply's one-workgroup kernel for LONG lists (k_apply_small,
 diagnostic build -DMPX_SMALL_STAMP=1); it does work only when a call puts more than 16 commands
 on a key (e.g. --keys 64), else every phase reads 0:
-  make -C minpaxos_amd variant_of FILE=apply_small NAME=sstamp DEFS=-DMPX_SMALL_STAMP=1
+  make -C minpaxos_amd variant_of FILE=apply_small.hip NAME=sstamp DEFS=-DMPX_SMALL_STAMP=1
   python tools/stamp_small.py minpaxos_amd/ab/libmpx_sstamp.so [--commands 5000] [--keys 64]
 """
 import argparse
