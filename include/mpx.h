@@ -53,6 +53,14 @@
  *     *_dev entry points take device pointers and a hipStream_t (passed as void*, NULL = the
  *     engine's stream) and are asynchronous; they never allocate or synchronise, so they can be
  *     captured into a hipGraph.
+ *   - alignment of *_dev pointers: arrays of 16- and 32-byte records (mpx_accept_reply,
+ *     mpx_inst_state, mpx_prepare_reply, mpx_prep_state, mpx_group_prep_state, mpx_var_frame,
+ *     mpx_log_rec, mpx_accept_msg, mpx_acceptor_state) 16 bytes - the kernels move them as 16-byte
+ *     vectors; every other array (mpx_prepare_reply_min, mpx_prepare_effect, mpx_peer_frame,
+ *     mpx_reply_rec, results, offsets, scalars, keys, values) the alignment of its C type; byte
+ *     arrays (op, decided / prepared flags, encoded output) any address. The two exceptions are
+ *     the decoders' input byte streams, which need 16 bytes (stated at their entry points). The
+ *     host-pointer forms take any alignment C allows: they stage into aligned device memory.
  *   - a handle is not re-entrant; use one handle per replica event loop / per GPU.
  *   - the tally (mpx_accept_tally_dev), CLASSIC prepare (mpx_prepare_select_dev), apply
  *     (mpx_apply_dev), group-step and durable-log replay (mpx_replay_durable_dev) kernels keep
@@ -281,7 +289,8 @@ int mpx_accept_tally(mpx_engine* eng, const mpx_accept_reply* recs, size_t n,
 
 /* device-pointer variant. st_in/st_out may alias; st_out[i] is written for every instance
  * that has at least one record (other entries untouched). d_scalars: int32 in/out
- * [0] = committedUpTo, [1..N] = peerCommits. d_decided (optional): as decided_out.        */
+ * [0] = committedUpTo, [1..N] = peerCommits. d_decided (optional): as decided_out, all n_inst
+ * bytes written. Alignment: d_recs, d_st_in, d_st_out 16 bytes; d_scalars 4; d_decided any. */
 int mpx_accept_tally_dev(mpx_engine* eng, const mpx_accept_reply* d_recs, size_t n,
                          const mpx_inst_state* d_st_in, mpx_inst_state* d_st_out,
                          size_t n_inst, int32_t inst_base, int32_t* d_scalars,
@@ -293,6 +302,9 @@ int mpx_accept_tally_dev(mpx_engine* eng, const mpx_accept_reply* d_recs, size_t
 int mpx_prepare_select(mpx_engine* eng, const mpx_prepare_reply* recs, size_t n,
                        mpx_prep_state* st, size_t n_inst, int32_t inst_base,
                        int32_t* default_ballot, uint8_t* prepared_out);
+/* device-pointer variant, as mpx_accept_tally_dev: d_st_in / d_st_out may alias, d_st_out[i] is
+ * written only for instances that have records. Alignment: d_recs, d_st_in, d_st_out 16 bytes;
+ * d_default_ballot 4; d_prepared any.                                                       */
 int mpx_prepare_select_dev(mpx_engine* eng, const mpx_prepare_reply* d_recs, size_t n,
                            const mpx_prep_state* d_st_in, mpx_prep_state* d_st_out,
                            size_t n_inst, int32_t inst_base, int32_t* d_default_ballot,
@@ -304,6 +316,8 @@ int mpx_prepare_select_dev(mpx_engine* eng, const mpx_prepare_reply* d_recs, siz
 int mpx_prepare_select_min(mpx_engine* eng, const mpx_prepare_reply_min* recs, size_t n,
                            const uint64_t* grp_rec_off, mpx_group_prep_state* gst,
                            size_t n_groups, int32_t* peer_commits, mpx_prepare_effect* eff);
+/* device-pointer variant; d_grp_rec_off is trusted. Alignment: d_gst 16 bytes; d_grp_rec_off 8;
+ * d_recs (24-byte records), d_peer_commits, d_eff 4.                                         */
 int mpx_prepare_select_min_dev(mpx_engine* eng, const mpx_prepare_reply_min* d_recs,
                                size_t n, const uint64_t* d_grp_rec_off,
                                mpx_group_prep_state* d_gst, size_t n_groups,
@@ -495,6 +509,9 @@ int mpx_decode_peer_stream(mpx_engine* eng, const uint8_t* buf, size_t len,
                            size_t other_cap, mpx_decode_result* res);
 /* scratch for mpx_decode_peer_stream_dev on buffers of up to max_len bytes (grows only)    */
 int mpx_decode_reserve(mpx_engine* eng, size_t max_len);
+/* device form: needs mpx_decode_reserve(len) first. d_buf must be 16-byte aligned (the tiles are
+ * loaded as 16-byte vectors; any other address is rejected with MPX_E_INVAL), d_ar 16 bytes,
+ * d_res 8, d_other 4. A capacity of 0 may come with a null pointer.                          */
 int mpx_decode_peer_stream_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
                                mpx_accept_reply* d_ar, size_t ar_cap, mpx_peer_frame* d_other,
                                size_t other_cap, mpx_decode_result* d_res, void* stream);
@@ -571,7 +588,10 @@ int mpx_decode_stream_reserve(mpx_engine* eng, size_t max_len);
 /* device form: frames d_buf[start, len) (start = 0, or a previous call's res.next) and
  * appends records at the indices the counts in *d_res (in/out: zero it for a new stream)
  * give; one call stops at the first frame that is a terminal (END / PARTIAL / MALFORMED) or
- * LONG. `out` is a host struct of device pointers.                                         */
+ * LONG. `out` is a host struct of device pointers. Needs mpx_decode_stream_reserve(len) first.
+ * d_buf must be 16-byte aligned (whatever `start` is; any other address is rejected with
+ * MPX_E_INVAL); out->ar, out->var and CLASSIC's out->prep 16 bytes; d_res 8; MIN's out->prep
+ * (24-byte records) and out->other 4. A capacity of 0 may come with a null pointer.          */
 int mpx_decode_stream_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len, size_t start,
                           const mpx_decode_out* out, mpx_stream_result* d_res, void* stream);
 
@@ -719,7 +739,9 @@ int mpx_encode_log(mpx_engine* eng, int format, const mpx_log_rec* recs, size_t 
                    const int64_t* val, size_t m, uint8_t* out, size_t out_cap,
                    uint64_t* rec_off);
 int mpx_encode_log_reserve(mpx_engine* eng, size_t max_n, size_t max_m);
-/* d_out must hold mpx_encode_log_bound(n, m) bytes; cmd_off is trusted (not validated)     */
+/* d_out must hold mpx_encode_log_bound(n, m) bytes, of which only [0, rec_off[n]) are written;
+ * cmd_off is trusted (not validated). Needs mpx_encode_log_reserve(n, m) first. Alignment:
+ * d_recs 16 bytes; d_cmd_off, d_key, d_val, d_rec_off 8; d_op and d_out any address.         */
 int mpx_encode_log_dev(mpx_engine* eng, int format, const mpx_log_rec* d_recs, size_t n,
                        const uint64_t* d_cmd_off, const uint8_t* d_op, const int64_t* d_key,
                        const int64_t* d_val, size_t m, uint8_t* d_out, uint64_t* d_rec_off,

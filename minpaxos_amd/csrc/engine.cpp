@@ -1033,6 +1033,8 @@ int mpx_decode_peer_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
     if (!d_res || (len && !d_buf) || (ar_cap && !d_ar) || (other_cap && !d_other))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
     CK(decode_limit(e, len));
+    if ((uintptr_t)d_buf % 16)
+        return fail(e, MPX_E_INVAL, "d_buf must be 16-byte aligned (tiles load 16 B vectors)");
     CK(reserved(e, e->decode_work, mpx::decode_work_bytes(len), "mpx_decode_peer_stream_dev",
                 "mpx_decode_reserve(len)"));
     HIPCHK(e, mpx::launch_decode_peer_stream(d_buf, len, d_ar, ar_cap, d_other, other_cap, d_res,
