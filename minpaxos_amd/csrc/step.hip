@@ -11,9 +11,9 @@
 //      on the same key (state.go:53-60).
 // Two kernels:
 //   k_group_fast     groups that fit one LDS image (<= 1024 replies, <= 256 instances,
-//                    <= 1024 commands, <= 256 table entries, <= 512 distinct keys). The replies
-//                    and instance state are loaded up front (the reply image goes to LDS), the
-//                    commands while the tally runs; the group's table becomes an LDS hash table
+//                    <= 1024 commands, <= 256 table entries, <= 512 distinct keys). Everything
+//                    the group reads is loaded up front in one batch (the reply image goes to
+//                    LDS, the commands stay in registers); the group's table becomes an LDS hash table
 //                    keyed by the 64-bit key and the commands are resolved by a chunk scan in
 //                    log order (see "fast path" below). Nothing is written until the group is
 //                    known to fit; a group that does not is appended to a work list instead.
@@ -288,6 +288,11 @@ struct FastCfg {
     // the 1024-key variant reads them from the input table instead: its 8 KB would hold the
     // workgroup at 3 per CU (41.7 KB), without them 4 fit (33.5 KB)
     static constexpr bool kFDvalLds = TB_ <= 512;
+    // one batch of loads for the whole group where the replies take at most four 16-byte loads
+    // per thread; the 2048-replies-by-256-threads variant keeps the commands in a second batch
+    // after the replies' staging and the values in a third after the tally (all at once: 89-93
+    // VGPRs, one workgroup per CU fewer)
+    static constexpr bool kFOneRound = R_ / T_ <= 4;
     static_assert(kFCmds % kFT == 0 && kFRecs % kFT == 0, "whole items per thread");
     static_assert(kFCmds / 32 <= kWave, "the new-key bitmap is scanned by one wave");
     static_assert(kWaveCmds < 2047, "kTabLp holds 1 + a wave-relative command index");
@@ -523,23 +528,31 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
     uint32_t ebits = 0;                                                  // error bits of this lane
 
     // ---- phase 0: one round of loads (indices clamped, not guarded: no branch splits the batch)
+    // Every global load of the group is issued here, back to back, before anything waits: the
+    // replies, the instance state, cmd_off, the table, the commands' opcodes, keys and values.
+    // vmcnt counts in order, so the first wait (the replies' staging into LDS) leaves every later
+    // load outstanding, and the whole group costs one round trip to memory. A group without
+    // replies or without commands still reads nothing from those arrays (they may end here): its
+    // loads go to this lane's instance state instead, which is always valid, and what they
+    // return is never used (every use below is predicated on p < nrec / on the executed range).
+    const bool own = (uint32_t)t < ipg;  // this lane owns instance t
+    const uint32_t ti = own ? (uint32_t)t : ipg - 1;
+    const int4* const stp = reinterpret_cast<const int4*>(b.st_in) + gi0 + ti;
     int4 rr[kFRecPer];
-    if (nrec) {  // uniform: groups without replies read nothing (the array may end here)
-        const uint32_t last = (uint32_t)nrec - 1;
+    {
+        const uint32_t last = nrec ? (uint32_t)nrec - 1 : 0u;
 #pragma unroll
         for (int k = 0; k < kFRecPer; ++k) {
             const uint32_t p = t + k * kFT;
-            rr[k] = ld_stream(reinterpret_cast<const int4*>(b.recs) + r0 + (p < last ? p : last));
+            const int4* const rp = reinterpret_cast<const int4*>(b.recs) + r0 + (p < last ? p : last);
+            rr[k] = ld_stream(nrec ? rp : stp);
         }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kFRecPer; ++k) rr[k] = make_int4(-1, 0, 0, 0);
     }
-    const bool own = (uint32_t)t < ipg;  // this lane owns instance t
-    const uint32_t ti = own ? (uint32_t)t : ipg - 1;
-    int4 st = ld_stream(reinterpret_cast<const int4*>(b.st_in) + gi0 + ti);
+    int4 st = ld_stream(stp);
     const uint32_t co = b.cmd_off[gi0 + ti];
-    const uint8_t hs = b.has_cmds ? b.has_cmds[gi0 + ti] : (uint8_t)1;
+    // (no has_cmds array: every instance has commands; the byte then read is cmd_off's)
+    const uint8_t hs0 = *(b.has_cmds ? b.has_cmds + gi0 + ti
+                                     : reinterpret_cast<const uint8_t*>(b.cmd_off + gi0 + ti));
     int64_t tk[kFTabPer], tv[kFTabPer];  // this lane's table entries t, t + T, ...
 #pragma unroll
     for (int k = 0; k < kFTabPer; ++k) {
@@ -548,6 +561,41 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         tk[k] = b.kv_key_in[ei];
         tv[k] = b.kv_val_in[ei];
     }
+    const uint32_t clast = ncmd ? ncmd - 1 : 0;
+    // wave w owns commands [256w, 256w + 256) in four chunks of 64: lane l of chunk k holds
+    // command cbase + 64k (the chunk scan below relies on this log order)
+    const uint32_t cbase = (uint32_t)(t - l) * kFPer + (uint32_t)l;
+    uint8_t o[kFPer];  // (separate registers until B1: packing them would wait for them)
+    int64_t ck[kFPer];
+    int64_t cv[kFPer];  // command values, stored to LDS after the tally
+    auto load_cmds = [&]() {
+#pragma unroll
+        for (int k = 0; k < kFPer; ++k) {
+            const uint32_t li = cbase + k * kWave;
+            const uint64_t ci = c_lo + (li < clast ? li : clast);
+            o[k] = ld_stream(ncmd ? b.op + ci : reinterpret_cast<const uint8_t*>(stp));
+        }
+#pragma unroll
+        for (int k = 0; k < kFPer; ++k) {
+            const uint32_t li = cbase + k * kWave;
+            const uint64_t ci = c_lo + (li < clast ? li : clast);
+            ck[k] = ld_stream(ncmd ? b.key + ci : reinterpret_cast<const int64_t*>(stp));
+        }
+    };
+    auto load_vals = [&]() {
+#pragma unroll
+        for (int k = 0; k < kFPer; ++k) {
+            const uint32_t li = cbase + k * kWave;
+            const uint64_t ci = c_lo + (li < clast ? li : clast);
+            cv[k] = ld_stream(ncmd ? b.val + ci : reinterpret_cast<const int64_t*>(stp));
+        }
+    };
+    if constexpr (Cfg::kFOneRound) {
+        load_cmds();
+        load_vals();
+    }
+    __builtin_amdgcn_sched_barrier(0);  // nothing below moves up between the loads
+    const uint8_t hs = b.has_cmds ? hs0 : (uint8_t)1;
     // LDS initialisation (regions outside the reply image)
 #pragma unroll
     for (int k = 0; k < (kFH + kFT - 1) / kFT; ++k)
@@ -573,23 +621,21 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
         if (MODE == MPX_MODE_CLASSIC) S.u.a.bal[p] = rr[k].y;
         S.u.a.idok[p] = (uint8_t)((idc << 1) | ((rr[k].w & 0xff) == 1 ? 1u : 0u));
     }
-    // command keys and opcodes: issued now, they arrive during the tally (the replies' registers
-    // are free again, so the two batches of loads are never in flight together). Values follow
-    // after the tally. Uniform guard: a group without commands reads nothing.
-    const uint32_t clast = ncmd ? ncmd - 1 : 0;
-    // wave w owns commands [256w, 256w + 256) in four chunks of 64: lane l of chunk k holds
-    // command cbase + 64k (the chunk scan below relies on this log order)
-    const uint32_t cbase = (uint32_t)(t - l) * kFPer + (uint32_t)l;
-    uint8_t o[kFPer];
-    int64_t ck[kFPer];
+    // every word of the replies stays allocated up to its staging: a word the mode does not read
+    // (MIN: the ballot) is otherwise handed to an address computation between the loads, which
+    // then waits for the load that still has to write it
 #pragma unroll
-    for (int k = 0; k < kFPer; ++k) {
-        const uint32_t li = cbase + k * kWave;
-        const uint64_t ci = c_lo + (li < clast ? li : clast);
-        o[k] = ncmd ? ld_stream(b.op + ci) : (uint8_t)0;
-        ck[k] = ncmd ? ld_stream(b.key + ci) : 0;
+    for (int k = 0; k < kFRecPer; ++k)
+        asm volatile("" ::"v"(rr[k].x), "v"(rr[k].y), "v"(rr[k].z), "v"(rr[k].w));
+    if constexpr (!Cfg::kFOneRound) {  // (the replies' registers are free again)
+        __builtin_amdgcn_sched_barrier(0);
+        load_cmds();
     }
+    // (fenced for the scheduler: packing the opcodes, or anything else that waits for the
+    // commands, stays behind the barrier)
+    __builtin_amdgcn_sched_barrier(0);
     __syncthreads();  // B1
+    __builtin_amdgcn_sched_barrier(0);
     STAMP(0);
 
     // ---- phase 1: reply ranges from head flags; the group's table into the dictionary ----------
@@ -737,12 +783,7 @@ __global__ __launch_bounds__(Cfg::kFT) void k_group_fast(mpx_group_batch b, int3
     // the last lane of each slot in each chunk) and the earlier waves (their tables, after B4).
     // Per command this yields the predecessor (state.Conflict) and the last PUT before it
     // (Execute's GET result); the key's last PUT overall gives its value after the step.
-    int64_t cv[kFPer];  // command values, stored to LDS once the lookup has covered their latency
-#pragma unroll
-    for (int k = 0; k < kFPer; ++k) {
-        const uint32_t li = cbase + k * kWave;
-        cv[k] = ncmd ? ld_stream(b.val + c_lo + (li < clast ? li : clast)) : 0;
-    }
+    if constexpr (!Cfg::kFOneRound) load_vals();  // (the lookup below covers their latency)
     uint32_t ops = 0;  // the four opcodes, one byte each
 #pragma unroll
     for (int k = 0; k < kFPer; ++k) ops |= (uint32_t)o[k] << (8 * k);
