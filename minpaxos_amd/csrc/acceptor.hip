@@ -234,7 +234,6 @@ struct ArFirstOut {
         first[i] = ex;
     }
 };
-uint64_t ar_al(uint64_t x) { return (x + 255) & ~255ull; }
 }  // namespace
 
 // destination of reply p of the call: 0 .. n_dest-1, or kArDest (skipped: reply_to < 0, past the
@@ -383,11 +382,21 @@ __global__ void k_ar_empty(uint64_t* dest_off, uint32_t n_dest) {
     for (uint32_t x = threadIdx.x; x <= n_dest; x += blockDim.x) dest_off[x] = 0;
 }
 
-uint64_t accept_replies_work_bytes(uint64_t n) {
-    const uint64_t tiles = (n + kArTile - 1) / kArTile;
-    const uint64_t h = (uint64_t)kArDest * (tiles ? tiles : 1);
-    return 2 * ar_al(h * 4) + ar_al(scan_scratch_bytes<uint32_t>(h));
-}
+namespace {
+struct ArWork {
+    uint32_t *hist, *first, *scan_tmp;
+    // (rows of kArDest whatever the call's n_dest, and a tile for an empty call)
+    ArWork(Carver& c, uint64_t n) {
+        const uint64_t tiles = (n + kArTile - 1) / kArTile;
+        const uint64_t h = (uint64_t)kArDest * (tiles ? tiles : 1);
+        hist = c.take<uint32_t>(h);
+        first = c.take<uint32_t>(h);
+        scan_tmp = (uint32_t*)c.take<char>(scan_scratch_bytes<uint32_t>(h));
+    }
+};
+}  // namespace
+
+uint64_t accept_replies_work_bytes(uint64_t n, Carver&& c) { return ArWork(c, n), c.bytes(); }
 
 hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replies,
                                         const int32_t* reply_to, uint64_t n, uint32_t n_dest,
@@ -398,23 +407,21 @@ hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replie
         k_ar_empty<<<1, 64, 0, stream>>>(dest_off, n_dest);
         return hipGetLastError();
     }
-    if (work_bytes < accept_replies_work_bytes(n)) return hipErrorInvalidValue;
+    Carver c(work);
+    const ArWork w(c, n);
+    if (work_bytes < c.bytes()) return hipErrorInvalidValue;
     const uint64_t tiles = (n + kArTile - 1) / kArTile;
     const uint64_t h = (uint64_t)n_dest * tiles;
-    char* w = (char*)work;
-    uint32_t* hist = (uint32_t*)w;
-    uint32_t* first = (uint32_t*)(w + ar_al((uint64_t)kArDest * tiles * 4));
-    uint32_t* tmp = (uint32_t*)(w + 2 * ar_al((uint64_t)kArDest * tiles * 4));
-    k_ar_count<<<(unsigned)tiles, kArBlock, 0, stream>>>(reply_to, n, n_dest, tiles, hist, err);
-    const hipError_t r =
-        device_scan(ArHistIn{hist}, ArFirstOut{first}, h, ScanSum32{}, 0u, tmp, stream);
+    k_ar_count<<<(unsigned)tiles, kArBlock, 0, stream>>>(reply_to, n, n_dest, tiles, w.hist, err);
+    const hipError_t r = device_scan(ArHistIn{w.hist}, ArFirstOut{w.first}, h, ScanSum32{}, 0u,
+                                     w.scan_tmp, stream);
     if (r != hipSuccess) return r;
     if (mode == MPX_MODE_MIN)
         k_ar_emit<MPX_ACCEPT_REPLY_FRAME_MIN><<<(unsigned)tiles, kArBlock, 0, stream>>>(
-            replies, reply_to, n, n_dest, tiles, first, out, dest_off, err);
+            replies, reply_to, n, n_dest, tiles, w.first, out, dest_off, err);
     else
         k_ar_emit<MPX_ACCEPT_REPLY_FRAME_CLASSIC><<<(unsigned)tiles, kArBlock, 0, stream>>>(
-            replies, reply_to, n, n_dest, tiles, first, out, dest_off, err);
+            replies, reply_to, n, n_dest, tiles, w.first, out, dest_off, err);
     return hipGetLastError();
 }
 

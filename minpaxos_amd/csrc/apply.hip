@@ -493,31 +493,27 @@ __global__ __launch_bounds__(256) void k_apply_commit(KvTable t, const uint64_t*
 }
 
 namespace {
-struct WorkLayout {
-    uint64_t skey_a, skey_b, lps, jkey, code, jkey_b, code_b, n_miss, tmp, tmp_bytes, total;
+struct SortedWork {  // the sort-based pipeline's scratch for chunks of m commands
+    uint64_t *skey_a, *skey_b;
+    int32_t* lps;
+    uint32_t *jkey, *code, *jkey_b, *code_b, *n_miss;
+    void* tmp;  // the two sorts' and the scan's, one after the other
+    uint64_t tmp_bytes;
+    SortedWork(Carver& c, uint64_t m) {
+        skey_a = c.take<uint64_t>(m);
+        skey_b = c.take<uint64_t>(m);
+        lps = c.take<int32_t>(m);
+        jkey = c.take<uint32_t>(m);
+        code = c.take<uint32_t>(m);
+        jkey_b = c.take<uint32_t>(m);
+        code_b = c.take<uint32_t>(m);
+        n_miss = c.take<uint32_t>(1);
+        tmp_bytes = std::max({radix_scratch_bytes<uint64_t, RsNoValue>(m),
+                              scan_scratch_bytes<SlotPos>(m),
+                              radix_scratch_bytes<uint32_t, uint32_t>(m)});
+        tmp = c.take<char>(tmp_bytes);
+    }
 };
-WorkLayout layout(uint64_t m) {
-    const uint64_t sort_tmp = radix_scratch_bytes<uint64_t, RsNoValue>(m);
-    const uint64_t scan_tmp = scan_scratch_bytes<SlotPos>(m);
-    const uint64_t back_tmp = radix_scratch_bytes<uint32_t, uint32_t>(m);
-    uint64_t t = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
-    t = t > back_tmp ? t : back_tmp;
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    WorkLayout w;
-    uint64_t o = 0;
-    w.skey_a = o; o += al(m * 8);
-    w.skey_b = o; o += al(m * 8);
-    w.lps = o; o += al(m * 4);
-    w.jkey = o; o += al(m * 4);
-    w.code = o; o += al(m * 4);
-    w.jkey_b = o; o += al(m * 4);
-    w.code_b = o; o += al(m * 4);
-    w.n_miss = o; o += al(4);
-    w.tmp_bytes = al(t);
-    w.tmp = o; o += w.tmp_bytes;
-    w.total = o;
-    return w;
-}
 
 unsigned grid_for(uint64_t n) {
     uint64_t b = (n + 255) / 256;
@@ -561,10 +557,11 @@ uint32_t hot_min(const ApplyOpts& o) {  // sample count (of 64K) that makes a ke
 
 bool apply_is_one_launch(const ApplyOpts& o, uint64_t m) { return m && use_small(o, m); }
 
-uint64_t apply_work_bytes(const KvTable& t, const ApplyOpts& o, uint64_t m) {
+uint64_t apply_work_bytes(const KvTable& t, const ApplyOpts& o, uint64_t m, Carver&& c) {
     if (use_small(o, m)) return 0;
     const uint64_t C = apply_chunk_commands(o.chunk, m);
-    return use_fast(t, o, m) ? apply_fast_work_bytes(t, C) : layout(C).total;
+    if (use_fast(t, o, m)) return apply_fast_work_bytes(t, C, c);
+    return SortedWork(c, C), c.bytes();
 }
 
 // Every m <= max_m must fit: each pipeline's need grows with m, so the largest call on either
@@ -589,29 +586,20 @@ hipError_t launch_apply(KvTable& t, const uint8_t* op, const int64_t* key, const
         return launch_apply_fast(t, op, key, val, m, ret, conf, C, w, hot_min(o), err, stream);
     // result codes carry a chunk index or a slot in 29 bits
     if (C > kPayloadMask || t.cap + 1 > kPayloadMask) return hipErrorInvalidValue;
-    const WorkLayout L = layout(C);
-    if (w.bytes < L.total) return hipErrorInvalidValue;
-    char* b = (char*)w.base;
-    uint64_t* skey_a = (uint64_t*)(b + L.skey_a);
-    uint64_t* skey_b = (uint64_t*)(b + L.skey_b);
-    int32_t* lps = (int32_t*)(b + L.lps);
-    uint32_t* jkey = (uint32_t*)(b + L.jkey);
-    uint32_t* code = (uint32_t*)(b + L.code);
-    uint32_t* jkey_b = (uint32_t*)(b + L.jkey_b);
-    uint32_t* code_b = (uint32_t*)(b + L.code_b);
-    void* tmp = b + L.tmp;
+    Carver c(w.base);
+    const SortedWork L(c, C);
+    if (w.bytes < c.bytes()) return hipErrorInvalidValue;
     const unsigned slot_bits = bits_for(t.cap + 2);
 
-    uint32_t* n_miss = (uint32_t*)(b + L.n_miss);
-    if (const hipError_t er = launch_epoch_next(t, n_miss, stream); er != hipSuccess) return er;
+    if (const hipError_t er = launch_epoch_next(t, L.n_miss, stream); er != hipSuccess) return er;
     // one chunk: one pass writes every sort key (PUTs insert, the rest probe; misses re-probed
     // after the pass, through lps as the miss list - lps is not live until the scan)
     const bool one = C >= m;
     if (one) {
-        k_kv_index<<<grid_for(m), 256, 0, stream>>>(t, op, key, m, err, skey_a, (uint32_t*)lps,
-                                                    n_miss);
-        k_kv_reprobe<<<grid_for(m), 256, 0, stream>>>(t, op, key, (const uint32_t*)lps, n_miss,
-                                                      skey_a);
+        k_kv_index<<<grid_for(m), 256, 0, stream>>>(t, op, key, m, err, L.skey_a, (uint32_t*)L.lps,
+                                                    L.n_miss);
+        k_kv_reprobe<<<grid_for(m), 256, 0, stream>>>(t, op, key, (const uint32_t*)L.lps, L.n_miss,
+                                                      L.skey_a);
     } else {
         k_kv_insert_puts<<<grid_for(m), 256, 0, stream>>>(t, op, key, m, err);
     }
@@ -619,27 +607,28 @@ hipError_t launch_apply(KvTable& t, const uint8_t* op, const int64_t* key, const
         const uint64_t n = m - c0 < C ? m - c0 : C;
         const unsigned g = grid_for(n);
         if (!one)
-            k_kv_lookup<<<g, 256, 0, stream>>>(t, op + c0, key + c0, n, skey_a);
-        hipError_t r = radix_sort<uint64_t, RsNoValue>(skey_a, skey_b, nullptr, nullptr, n, 32u,
-                                                       32u + slot_bits, tmp, L.tmp_bytes, stream);
+            k_kv_lookup<<<g, 256, 0, stream>>>(t, op + c0, key + c0, n, L.skey_a);
+        hipError_t r = radix_sort<uint64_t, RsNoValue>(L.skey_a, L.skey_b, nullptr, nullptr, n, 32u,
+                                                       32u + slot_bits, L.tmp, L.tmp_bytes, stream);
         if (r != hipSuccess) return r;
-        r = device_scan(PutPosIn{skey_b}, LastPutOut{lps}, n, SegMax{},
-                        SlotPos{0xFFFFFFFFu, -1}, (SlotPos*)tmp, stream);
+        r = device_scan(PutPosIn{L.skey_b}, LastPutOut{L.lps}, n, SegMax{},
+                        SlotPos{0xFFFFFFFFu, -1}, (SlotPos*)L.tmp, stream);
         if (r != hipSuccess) return r;
-        k_apply_finish<<<g, 256, 0, stream>>>(t, skey_b, lps, n, jkey, code);
+        k_apply_finish<<<g, 256, 0, stream>>>(t, L.skey_b, L.lps, n, L.jkey, L.code);
         const unsigned jb = bits_for(n);
-        const uint32_t *jk = jkey, *cd = code;  // one emit group: LDS placement alone suffices
+        const uint32_t *jk = L.jkey, *cd = L.code;  // one emit group: LDS placement alone suffices
         if (jb > (unsigned)kEmitBits) {
-            r = radix_sort<uint32_t, uint32_t>(jkey, jkey_b, code, code_b, n, (unsigned)kEmitBits,
-                                               jb, tmp, L.tmp_bytes, stream);
+            r = radix_sort<uint32_t, uint32_t>(L.jkey, L.jkey_b, L.code, L.code_b, n,
+                                               (unsigned)kEmitBits, jb, L.tmp, L.tmp_bytes,
+                                               stream);
             if (r != hipSuccess) return r;
-            jk = jkey_b;
-            cd = code_b;
+            jk = L.jkey_b;
+            cd = L.code_b;
         }
         const unsigned eg = (unsigned)((n + kEmitGroup - 1) / kEmitGroup);
         k_apply_emit<<<eg, 256, 0, stream>>>(t, jk, cd, n, val + c0, ret + c0,
                                              conf ? conf + c0 : nullptr);
-        k_apply_commit<<<g, 256, 0, stream>>>(t, skey_b, lps, n, val + c0);
+        k_apply_commit<<<g, 256, 0, stream>>>(t, L.skey_b, L.lps, n, val + c0);
     }
     return hipGetLastError();
 }

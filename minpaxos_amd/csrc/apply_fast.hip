@@ -1238,7 +1238,6 @@ __global__ __launch_bounds__(kLT) void k_ap_resolve_list(ApGeo g, KvTable t,
                 int64_t nval[kLPer];
 #pragma unroll
                 for (int hh = 0; hh < kLPer; ++hh) {
-                    const uint32_t i = hh * kLT + tid;
                     nval[hh] = 0;
                     const bool isput = (cl[hh] & 2u) != 0, isget = (cl[hh] & 4u) != 0;
                     int64_t ret = 0;
@@ -1404,11 +1403,6 @@ struct EmitLds {
     uint32_t hfl[kHMax];
     int64_t iret[kTL];     // the tile's cold results in image order (bin runs)
     uint8_t iconf[kTL];
-    // unused since the partition-order gather went; dropping them shrinks the kernel's LDS
-    // (78656 -> 72448 bytes), a device-code change left to a commit that measures it
-    uint16_t lst[kMaxBins];
-    uint32_t dof[kMaxBins];
-    uint32_t wsum[kTW];
 };
 
 __global__ __launch_bounds__(kTT) void k_ap_emit(ApGeo g, const uint8_t* __restrict__ op,
@@ -1545,9 +1539,15 @@ emit_out:
 
 // ---- launcher ---------------------------------------------------------------------------------
 namespace {
-struct FastLayout {
-    uint64_t gk, gc, rows, part, ctot, bin_start, img, lrow, runs, ipos, tcold, r_ret, r_conf, hot,
-        total;
+struct FastWork {  // the partitioned pipeline's scratch for chunks of c commands
+    int64_t *gk, *r_ret;
+    uint32_t *gc, *rows, *part, *ctot, *bin_start, *tcold;
+    uint16_t *lrow, *ipos;
+    int4* img;
+    uint2* runs;
+    uint8_t* r_conf;
+    ApHot* hot;
+    FastWork(Carver& c, const KvTable& t, uint64_t n);
 };
 
 ApGeo geo_for(const KvTable& t, uint64_t n) {
@@ -1567,29 +1567,24 @@ ApGeo geo_for(const KvTable& t, uint64_t n) {
     return g;
 }
 
-FastLayout fast_layout(const KvTable& t, uint64_t c) {
-    const ApGeo g = geo_for(t, c);
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    FastLayout L{};
-    uint64_t o = 0;
-    L.gk = o; o += al((uint64_t)kGTab * 8);
-    L.gc = o; o += al((uint64_t)kGTab * 4);
-    L.rows = o; o += al((uint64_t)g.tiles * g.rowlen * 4);
-    L.part = o; o += al((uint64_t)kScanGroups * g.rowlen * 4);
-    L.ctot = o; o += al((uint64_t)g.nbin * 4);
-    L.bin_start = o; o += al(((uint64_t)g.nbin + 1) * 4);
-    L.img = o; o += al((uint64_t)g.tiles * kTL * 16);
-    L.lrow = o; o += al((uint64_t)g.tiles * g.nbin * 2);
-    L.runs = o; o += al((uint64_t)g.tiles * g.nbin * 8);
-    L.ipos = o; o += al(c * 2);
-    L.tcold = o; o += al((uint64_t)g.tiles * 4);
+FastWork::FastWork(Carver& c, const KvTable& t, uint64_t n) {
+    const ApGeo g = geo_for(t, n);
+    gk = c.take<int64_t>(kGTab);
+    gc = c.take<uint32_t>(kGTab);
+    rows = c.take<uint32_t>((uint64_t)g.tiles * g.rowlen);
+    part = c.take<uint32_t>((uint64_t)kScanGroups * g.rowlen);
+    ctot = c.take<uint32_t>(g.nbin);
+    bin_start = c.take<uint32_t>((uint64_t)g.nbin + 1);
+    img = c.take<int4>((uint64_t)g.tiles * kTL);
+    lrow = c.take<uint16_t>((uint64_t)g.tiles * g.nbin);
+    runs = c.take<uint2>((uint64_t)g.tiles * g.nbin);
+    ipos = c.take<uint16_t>(n);
+    tcold = c.take<uint32_t>(g.tiles);
     // results: at image positions, + the spare result (see k_ap_resolve_list)
     const uint64_t nres = (uint64_t)g.tiles * kTL + 1;
-    L.r_ret = o; o += al(nres * 8);
-    L.r_conf = o; o += al(nres);
-    L.hot = o; o += al(sizeof(ApHot));
-    L.total = o;
-    return L;
+    r_ret = c.take<int64_t>(nres);
+    r_conf = c.take<uint8_t>(nres);
+    hot = c.take<ApHot>(1);
 }
 }  // namespace
 
@@ -1597,7 +1592,9 @@ bool apply_fast_ok(const KvTable& t) {
     return t.lgnb >= 2 && t.lgnb - lgbpb_for(t.lgnb) <= (uint32_t)(kLgMaxBins + kLgMaxSub);
 }
 
-uint64_t apply_fast_work_bytes(const KvTable& t, uint64_t c) { return fast_layout(t, c).total; }
+uint64_t apply_fast_work_bytes(const KvTable& t, uint64_t n, Carver& c) {
+    return FastWork(c, t, n), c.bytes();
+}
 
 __global__ __launch_bounds__(256) void k_ap_preinsert(KvTable t, const uint8_t* __restrict__ op,
                                                       const int64_t* __restrict__ key, uint64_t m,
@@ -1611,23 +1608,9 @@ hipError_t launch_apply_fast(KvTable& t, const uint8_t* op, const int64_t* key, 
                              uint64_t m, int64_t* ret, uint8_t* conf, uint64_t C, ApplyWork& w,
                              uint32_t hot_min, uint32_t* err, hipStream_t stream) {
     if (C >= (1ull << 31)) return hipErrorInvalidValue;
-    const FastLayout L = fast_layout(t, C);
-    if (w.bytes < L.total) return hipErrorInvalidValue;
-    char* b = (char*)w.base;
-    int64_t* gk = (int64_t*)(b + L.gk);
-    uint32_t* gc = (uint32_t*)(b + L.gc);
-    uint32_t* rows = (uint32_t*)(b + L.rows);
-    uint32_t* part = (uint32_t*)(b + L.part);
-    uint32_t* ctot = (uint32_t*)(b + L.ctot);
-    uint32_t* bin_start = (uint32_t*)(b + L.bin_start);
-    int4* img = (int4*)(b + L.img);
-    uint16_t* lrow = (uint16_t*)(b + L.lrow);
-    uint2* runs = (uint2*)(b + L.runs);
-    uint16_t* ipos = (uint16_t*)(b + L.ipos);
-    uint32_t* tcold = (uint32_t*)(b + L.tcold);
-    int64_t* r_ret = (int64_t*)(b + L.r_ret);
-    uint8_t* r_conf = (uint8_t*)(b + L.r_conf);
-    ApHot* hot = (ApHot*)(b + L.hot);
+    Carver c(w.base);
+    const FastWork W(c, t, C);
+    if (w.bytes < c.bytes()) return hipErrorInvalidValue;
 
     if (const hipError_t er = launch_epoch_next(t, nullptr, stream); er != hipSuccess) return er;
     if (C < m) {
@@ -1641,24 +1624,26 @@ hipError_t launch_apply_fast(KvTable& t, const uint8_t* op, const int64_t* key, 
         const ApGeo g = geo_for(t, n);
         const uint32_t tab = gtab_for(n);
         if (hot_min) {
-            k_ap_sclear<<<kSampGrid, 256, 0, stream>>>(gk, gc, tab);
-            k_ap_sample<<<kSampGrid, 256, 0, stream>>>(key + c0, n, hot_min, gk, gc, tab);
+            k_ap_sclear<<<kSampGrid, 256, 0, stream>>>(W.gk, W.gc, tab);
+            k_ap_sample<<<kSampGrid, 256, 0, stream>>>(key + c0, n, hot_min, W.gk, W.gc, tab);
         }
-        k_ap_select<<<1, kTT, 0, stream>>>(t, gk, gc, hot_min, tab, hot);
-        k_ap_scatter<<<kScatterGrid, kTT, 0, stream>>>(g, op + c0, key + c0, val + c0, n, rows,
-                                                       lrow, hot, img, ipos, tcold);
-        k_ap_scan_part<<<g.ng, 256, 0, stream>>>(g, rows, part, hot);
-        k_ap_scan_top<<<(g.rowlen + kTopCols - 1) / kTopCols, kTT, 0, stream>>>(g, part, ctot, hot);
-        k_ap_scan_bins<<<1, kTT, 0, stream>>>(g, ctot, bin_start);
-        k_ap_scan_rows<<<g.ng, 256, 0, stream>>>(g, rows, part, bin_start, hot);
+        k_ap_select<<<1, kTT, 0, stream>>>(t, W.gk, W.gc, hot_min, tab, W.hot);
+        k_ap_scatter<<<kScatterGrid, kTT, 0, stream>>>(g, op + c0, key + c0, val + c0, n, W.rows,
+                                                       W.lrow, W.hot, W.img, W.ipos, W.tcold);
+        k_ap_scan_part<<<g.ng, 256, 0, stream>>>(g, W.rows, W.part, W.hot);
+        k_ap_scan_top<<<(g.rowlen + kTopCols - 1) / kTopCols, kTT, 0, stream>>>(g, W.part, W.ctot,
+                                                                                W.hot);
+        k_ap_scan_bins<<<1, kTT, 0, stream>>>(g, W.ctot, W.bin_start);
+        k_ap_scan_rows<<<g.ng, 256, 0, stream>>>(g, W.rows, W.part, W.bin_start, W.hot);
         k_ap_runs<<<dim3((g.tiles + kRunT - 1) / kRunT, (g.nbin + kRunB - 1) / kRunB), 256, 0,
-                    stream>>>(g, rows, lrow, runs);
+                    stream>>>(g, W.rows, W.lrow, W.runs);
         const uint32_t spare = g.tiles * (uint32_t)kTL;
-        k_ap_resolve_list<<<g.nbin, kLT, 0, stream>>>(g, t, bin_start, runs, img, r_ret, r_conf,
-                                                      spare, hot, err);
-        k_ap_hot_commit<<<1, kHMax, 0, stream>>>(t, val + c0, hot, err);
-        k_ap_emit<<<g.tiles, kTT, 0, stream>>>(g, op + c0, val + c0, n, ipos, tcold, r_ret, r_conf, rows,
-                                               bin_start, hot, ret + c0, conf ? conf + c0 : nullptr);
+        k_ap_resolve_list<<<g.nbin, kLT, 0, stream>>>(g, t, W.bin_start, W.runs, W.img, W.r_ret,
+                                                      W.r_conf, spare, W.hot, err);
+        k_ap_hot_commit<<<1, kHMax, 0, stream>>>(t, val + c0, W.hot, err);
+        k_ap_emit<<<g.tiles, kTT, 0, stream>>>(g, op + c0, val + c0, n, W.ipos, W.tcold, W.r_ret,
+                                               W.r_conf, W.rows, W.bin_start, W.hot, ret + c0,
+                                               conf ? conf + c0 : nullptr);
     }
     return hipGetLastError();
 }

@@ -203,8 +203,7 @@ __device__ __forceinline__ void probe_cmd(const KvTable& t, uint32_t tag, uint8_
 __global__ __launch_bounds__(kProbeBlock) void k_small_probe(KvTable t, const uint8_t* __restrict__ op,
                                                        const int64_t* __restrict__ key,
                                                        const int64_t* __restrict__ val, uint32_t m,
-                                                       int64_t* __restrict__ ret, uint32_t* err,
-                                                       bool host_out) {
+                                                       int64_t* __restrict__ ret, uint32_t* err) {
     const uint32_t p = blockIdx.x * kProbeBlock + threadIdx.x;
     if (p >= m) return;
     const uint32_t tag = call_tag(t);
@@ -216,9 +215,6 @@ __global__ __launch_bounds__(kProbeBlock) void k_small_probe(KvTable t, const ui
     reinterpret_cast<int64_t*>(t.probe + kSmallValOff)[p] = v;
     reinterpret_cast<uint8_t*>(t.probe + kSmallOpOff)[p] = o;
     probe_cmd(t, tag, o, k, v, p, ret, err);
-    // host-mapped results: performed at system scope before the kernel ends, so the walk kernel's
-    // completion flag (stored after its own results) can never overtake them
-    if (host_out) __threadfence_system();
 }
 
 // ---- 2. the lookups that met a free slot, again now that every claim of the call is in --------
@@ -330,14 +326,6 @@ __device__ __forceinline__ void walk_one(const KvTable& t, const uint8_t* __rest
 // The call's last workgroup also closes it: the LONG count and the ticket back to 0 and the next
 // call's tag; after the call with the last tag every list head is cleared and the tags restart at
 // 1 (once per 2^18 - 1 calls: one workgroup's pass over the heads). All threads call it.
-// the host form's completion flag: every result of the call is visible to the host before it
-__device__ __forceinline__ void signal_done(uint32_t* done, uint32_t seq) {
-    if (!done) return;
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 __device__ __forceinline__ void end_of_call(const KvTable& t, uint32_t tag) {
     __syncthreads();  // every thread has read the control words
     const bool wrap = tag + 1u >= kSmallTagMax;
@@ -346,9 +334,6 @@ __device__ __forceinline__ void end_of_call(const KvTable& t, uint32_t tag) {
     }
     if (threadIdx.x == 0) {
         (void)atomic_take(&t.probe[kCtlOff]);
-        // (the removed grid barrier's counter: nothing raises it; the reset stays until a
-        // commit that may change device code)
-        (void)atomic_take(&t.probe[kCtlOff + 3]);
         t.probe[kCtlOff + 1] = wrap ? 0u : tag;
     }
 }
@@ -634,8 +619,8 @@ __device__ void long_lists(SmallLds& S, const KvTable& t, const uint8_t* __restr
 __global__ __launch_bounds__(kSmT) void k_small_walk(KvTable t, const uint8_t* __restrict__ op,
                                                      const int64_t* __restrict__ val, uint32_t m,
                                                      int64_t* __restrict__ ret,
-                                                     uint8_t* __restrict__ conf, uint32_t* done,
-                                                     uint32_t seq, const int64_t* __restrict__ key,
+                                                     uint8_t* __restrict__ conf,
+                                                     const int64_t* __restrict__ key,
                                                      uint32_t* err) {
     __shared__ SmallLds S;
     {
@@ -647,14 +632,12 @@ __global__ __launch_bounds__(kSmT) void k_small_walk(KvTable t, const uint8_t* _
             if (bl) atomic_add_done(&t.probe[kCtlOff], (uint32_t)popc(bl));
         }
     }
-    if (done) __threadfence_system();  // this workgroup's host-mapped results, before its ticket
     if (!last_workgroup(&t.probe[kCtlOff + 2])) return;
     const uint32_t n_long = __hip_atomic_load(&t.probe[kCtlOff], __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t tag = call_tag(t);
     if (n_long) long_lists(S, t, op, val, m, ret, conf, nullptr);  // (else every list was walked)
     end_of_call(t, tag);
-    signal_done(done, seq);
 }
 
 // ---- the one-launch form (device-resident commands: mpx_apply_dev) -----------------------------
@@ -953,10 +936,10 @@ extern "C" int mpx_debug_small_stamps(unsigned long long* out16, int reset) {
 
 hipError_t launch_apply_small(KvTable& t, const uint8_t* op, const int64_t* key, const int64_t* val,
                               uint64_t m, int64_t* ret, uint8_t* conf, uint32_t* err,
-                              hipStream_t stream, uint32_t* done, uint32_t seq, bool host_io) {
+                              hipStream_t stream, bool host_io) {
     if (!m) return hipSuccess;
     if (m > (uint64_t)kSmMax || t.cap >= 0x7FFFFFFEull) return hipErrorInvalidValue;
-    if (!host_io && !done) {
+    if (!host_io) {
         // a power of two of partitions, about kPartCmds commands each
         unsigned np = 1;
         while (np < kPartMax && np * kPartCmds < m) np <<= 1;
@@ -967,11 +950,10 @@ hipError_t launch_apply_small(KvTable& t, const uint8_t* op, const int64_t* key,
     const int64_t* d_key = reinterpret_cast<const int64_t*>(t.probe + kSmallKeyOff);
     const int64_t* d_val = reinterpret_cast<const int64_t*>(t.probe + kSmallValOff);
     const uint8_t* d_op = reinterpret_cast<const uint8_t*>(t.probe + kSmallOpOff);
-    k_small_probe<<<g, kProbeBlock, 0, stream>>>(t, op, key, val, (uint32_t)m, ret, err,
-                                                 done != nullptr);
+    k_small_probe<<<g, kProbeBlock, 0, stream>>>(t, op, key, val, (uint32_t)m, ret, err);
     k_small_reprobe<<<g, kProbeBlock, 0, stream>>>(t, d_key, (uint32_t)m);
     k_small_walk<<<(unsigned)((m + kSmT - 1) / kSmT), kSmT, 0, stream>>>(
-        t, d_op, d_val, (uint32_t)m, ret, conf, done, seq, d_key, err);
+        t, d_op, d_val, (uint32_t)m, ret, conf, d_key, err);
     return hipGetLastError();
 }
 

@@ -603,36 +603,44 @@ __global__ void k_dec_empty(mpx_decode_result* res) {
     res->stop_code = -1;
 }
 
-uint64_t decode_work_bytes(uint64_t len) {
-    const uint64_t tiles = (len + kTileBytes - 1) / kTileBytes;
-    const uint64_t groups = (tiles + kGroupTiles - 1) / kGroupTiles;
-    return (tiles * (kEntries + 1) + groups * (kEntries + 1)) * sizeof(GEntry) +
-           tiles * kTileLanes * sizeof(ulonglong2) + 256;
-}
+namespace {
+struct DecWork {
+    GEntry *tmap, *tres, *gmap, *gres;
+    ulonglong2* xmap;
+    uint64_t tiles, groups;  // (a call's fit 32 bits: len <= MPX_DECODE_MAX_BYTES)
+    DecWork(Carver& c, uint64_t len) {
+        tiles = (len + kTileBytes - 1) / kTileBytes;
+        groups = (tiles + kGroupTiles - 1) / kGroupTiles;
+        tmap = c.take<GEntry>(tiles * kEntries);
+        tres = c.take<GEntry>(tiles);
+        gmap = c.take<GEntry>(groups * kEntries);
+        gres = c.take<GEntry>(groups);
+        xmap = c.take<ulonglong2>(tiles * kTileLanes);
+    }
+};
+}  // namespace
+
+uint64_t decode_work_bytes(uint64_t len, Carver&& c) { return DecWork(c, len), c.bytes(); }
 
 hipError_t launch_decode_peer_stream(const uint8_t* buf, uint64_t len, mpx_accept_reply* ar_out,
                                      uint64_t ar_cap, mpx_peer_frame* oth_out, uint64_t oth_cap,
                                      mpx_decode_result* res, void* work, uint64_t work_bytes,
                                      hipStream_t stream) {
     if (len > (uint64_t)MPX_DECODE_MAX_BYTES) return hipErrorInvalidValue;
-    if (work_bytes < decode_work_bytes(len)) return hipErrorInvalidValue;
+    Carver c(work);
+    const DecWork w(c, len);
+    if (work_bytes < c.bytes()) return hipErrorInvalidValue;
     if (len == 0) {
         k_dec_empty<<<1, 1, 0, stream>>>(res);
         return hipGetLastError();
     }
-    const uint32_t tiles = (uint32_t)((len + kTileBytes - 1) / kTileBytes);
-    const uint32_t groups = (tiles + kGroupTiles - 1) / kGroupTiles;
-    GEntry* tmap = (GEntry*)work;
-    GEntry* tres = tmap + (uint64_t)tiles * kEntries;
-    GEntry* gmap = tres + tiles;
-    GEntry* gres = gmap + (uint64_t)groups * kEntries;
-    ulonglong2* xmap = (ulonglong2*)(((uintptr_t)(gres + groups) + 15) & ~(uintptr_t)15);
-    k_dec_tile_maps<<<tiles, kTileLanes, 0, stream>>>(buf, len, tmap, xmap);
-    k_dec_group_maps<<<groups, 256, 0, stream>>>(tmap, tiles, gmap);
-    k_dec_walk<<<1, 256, 0, stream>>>(gmap, groups, len, buf, gres, res);
-    k_dec_tile_entries<<<groups, 256, 0, stream>>>(tmap, tiles, gres, tres);
-    k_dec_emit<<<tiles, kTileLanes, 0, stream>>>(buf, len, tres, xmap, ar_out, ar_cap, oth_out,
-                                                 oth_cap);
+    const uint32_t tiles = (uint32_t)w.tiles, groups = (uint32_t)w.groups;
+    k_dec_tile_maps<<<tiles, kTileLanes, 0, stream>>>(buf, len, w.tmap, w.xmap);
+    k_dec_group_maps<<<groups, 256, 0, stream>>>(w.tmap, tiles, w.gmap);
+    k_dec_walk<<<1, 256, 0, stream>>>(w.gmap, groups, len, buf, w.gres, res);
+    k_dec_tile_entries<<<groups, 256, 0, stream>>>(w.tmap, tiles, w.gres, w.tres);
+    k_dec_emit<<<tiles, kTileLanes, 0, stream>>>(buf, len, w.tres, w.xmap, ar_out, ar_cap,
+                                                 oth_out, oth_cap);
     return hipGetLastError();
 }
 

@@ -26,8 +26,8 @@ struct DevBuf {
     size_t cap = 0;
 };
 
-// pinned, GPU-mapped staging of a replica-batch apply: [error word | completion flag] (a cache
-// line each), then op (cap rounded to 16), key, val, ret (cap each) and conf
+// pinned, GPU-mapped staging of a replica-batch apply: the error word in a 128-byte header, then
+// op (cap rounded to 16), key, val, ret (cap each) and conf
 struct PinIo {
     uint8_t* p = nullptr;
     size_t cap = 0;  // commands
@@ -35,7 +35,6 @@ struct PinIo {
 constexpr size_t kPinHdr = 128;
 struct PinView {
     volatile uint32_t* err;
-    volatile uint32_t* done;
     uint8_t* op;
     int64_t* key;
     int64_t* val;
@@ -46,7 +45,6 @@ PinView pin_view_at(uint8_t* base, size_t cap) {
     const size_t a16 = (cap + 15) & ~(size_t)15;
     PinView v;
     v.err = (volatile uint32_t*)base;
-    v.done = (volatile uint32_t*)(base + 64);
     v.op = base + kPinHdr;
     v.key = (int64_t*)(v.op + a16);
     v.val = v.key + cap;
@@ -80,7 +78,6 @@ struct mpx_engine {
     // commands from and writes the results to (no DMA copies on the call's path)
     PinIo pin_io;       // mpx_apply's (copies in and out)
     PinIo pin_staged;   // mpx_apply_buffers / mpx_apply_staged's (the caller fills it)
-    uint32_t small_seq = 0;  // the host form's completion flag value of the last call
     // group-step work list (groups the fast kernel hands to the general kernel) + its count
     DevBuf worklist;
     uint32_t* d_wcount = nullptr;
@@ -307,21 +304,16 @@ int pin_grow(mpx_engine* e, PinIo& p, size_t m) {
 }
 
 // the replica-batch kernels on m commands in pinned staging p, results back in it; returns once
-// the stream is done. (A completion flag in the pinned staging, polled by the host, was measured
-// and removed: 40.6-45.0 vs 32.0-37.9 us per 5000-command host call, profiles/r04/replica - the
-// kernels' per-thread system fences cost more than the stream wait's wake-up. The kernels' done /
-// seq parameters remain.)
+// the stream is done (DESIGN section 9 records the rejected alternative to the stream wait)
 int run_pinned(mpx_engine* e, const PinIo& p, size_t m, bool want_conf) {
     const PinView v = pin_view(p);
     *v.err = 0u;
     void* dp = nullptr;
     HIPCHK(e, hipHostGetDevicePointer(&dp, p.p, 0));
     const PinView d = pin_view_at((uint8_t*)dp, p.cap);
-    uint32_t seq = ++e->small_seq;
-    if (!seq) seq = e->small_seq = 1;  // 0 never marks a finished call
     HIPCHK(e, mpx::launch_apply_small(e->kv, d.op, d.key, d.val, m, d.ret,
                                       want_conf ? d.conf : nullptr, (uint32_t*)d.err, e->stream,
-                                      /*done=*/nullptr, seq, /*host_io=*/true));
+                                      /*host_io=*/true));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return check_errword(e, *v.err);
 }
@@ -1103,7 +1095,7 @@ int mpx_decode_stream_dev(mpx_engine* e, const uint8_t* d_buf, size_t len, size_
                 "mpx_decode_stream_reserve(len)"));
     const mpx::StreamOuts o{out->ar, out->ar_cap, out->prep, out->prep_cap, out->var,
                             out->var_cap, out->other, out->other_cap};
-    HIPCHK(e, mpx::launch_decode_stream(e->cfg.mode, 0, d_buf, len, start, o, d_res,
+    HIPCHK(e, mpx::launch_decode_stream(e->cfg.mode, d_buf, len, start, o, d_res,
                                         e->stream_work.p, e->stream_work.cap, pick(e, stream)));
     return MPX_OK;
 }

@@ -26,6 +26,7 @@
 // id with the reply index as payload, then each block gathers 256 replies, assembles their
 // encodings in LDS and stores the 6400-byte run with 16-byte vector stores.
 // client_off[c] = byte offset of client c's run; client_off[n_clients] = 25 n.
+#include <algorithm>
 #include <cstring>
 
 #include "common.hpp"
@@ -394,13 +395,33 @@ __global__ __launch_bounds__(kFanThreads) void k_fan_scatter(
     }
 }
 
-uint64_t fanout_work_bytes(uint64_t n) {
-    const uint64_t m = n ? n : 1;
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t radix = 4 * al(m * 4) + al(radix_scratch_bytes<uint32_t, uint32_t>(m));
-    const uint64_t h = (uint64_t)kFanMaxClients * fan_plan(m).slices;
-    const uint64_t counting = 2 * al(h * 4) + al(scan_scratch_bytes<uint32_t>(h));
-    return radix > counting ? radix : counting;
+namespace {
+// two alternative carve-ups of the one buffer: the counting path's (up to kFanMaxClients clients)
+// and the radix path's; c ends at the larger of the two
+struct FanWork {
+    uint32_t *hist, *first, *scan_tmp;
+    uint32_t *skeys, *perm, *keys_in, *idx_in;
+    void* sort_tmp;
+    uint64_t sort_tmp_bytes;
+    FanWork(Carver& c, uint64_t n, uint32_t n_clients) {
+        const uint64_t m = n ? n : 1, h = (uint64_t)n_clients * fan_plan(m).slices;
+        Carver r = c;
+        hist = c.take<uint32_t>(h);
+        first = c.take<uint32_t>(h);
+        scan_tmp = (uint32_t*)c.take<char>(scan_scratch_bytes<uint32_t>(h));
+        skeys = r.take<uint32_t>(m);
+        perm = r.take<uint32_t>(m);
+        keys_in = r.take<uint32_t>(m);
+        idx_in = r.take<uint32_t>(m);
+        sort_tmp_bytes = radix_scratch_bytes<uint32_t, uint32_t>(m);
+        sort_tmp = r.take<char>(sort_tmp_bytes);
+        if (r.bytes() > c.bytes()) c = r;
+    }
+};
+}  // namespace
+
+uint64_t fanout_work_bytes(uint64_t n, Carver&& c) {
+    return FanWork(c, n, kFanMaxClients), c.bytes();
 }
 
 hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t n_clients,
@@ -408,46 +429,39 @@ hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t
                                  void* work, uint64_t work_bytes, uint32_t* err,
                                  hipStream_t stream) {
     if (!n_clients || n >= (1ull << 32)) return hipErrorInvalidValue;
-    if (work_bytes < fanout_work_bytes(n)) return hipErrorInvalidValue;
+    Carver c(work);
+    const FanWork w(c, n, std::min(n_clients, kFanMaxClients));
+    // (fewer clients are still refused by what a reservation for n replies holds)
+    if (work_bytes < std::max(c.bytes(), fanout_work_bytes(n))) return hipErrorInvalidValue;
     if (n == 0) {
         k_fan_empty<<<1, 256, 0, stream>>>(client_off, n_clients);
         return hipGetLastError();
     }
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    char* w = (char*)work;
     if (n_clients <= kFanMaxClients) {
         const FanPlan p = fan_plan(n);
         const uint64_t h = (uint64_t)n_clients * p.slices;
-        uint32_t* hist = (uint32_t*)w;
-        uint32_t* first = (uint32_t*)(w + al(h * 4));
-        uint32_t* tmp = (uint32_t*)(w + 2 * al(h * 4));
         k_fan_count<<<p.slices, kFanThreads, 0, stream>>>(recs, n, p.per_slice, n_clients,
-                                                          p.slices, hist, err);
-        const hipError_t r = device_scan(HistIn{hist}, FirstOut{first}, h, ScanSum32{}, 0u, tmp,
-                                         stream);
+                                                          p.slices, w.hist, err);
+        const hipError_t r = device_scan(HistIn{w.hist}, FirstOut{w.first}, h, ScanSum32{}, 0u,
+                                         w.scan_tmp, stream);
         if (r != hipSuccess) return r;
         k_fan_scatter<<<p.slices, kFanThreads, 0, stream>>>(recs, n, p.per_slice, n_clients,
-                                                            p.slices, first, ok, leader, out,
+                                                            p.slices, w.first, ok, leader, out,
                                                             client_off, err);
         return hipGetLastError();
     }
-    uint32_t* skeys = (uint32_t*)w;
-    uint32_t* perm = (uint32_t*)(w + al(n * 4));
-    uint32_t* keys_in = (uint32_t*)(w + 2 * al(n * 4));
-    uint32_t* idx_in = (uint32_t*)(w + 3 * al(n * 4));
-    void* tmp = w + 4 * al(n * 4);
-    const uint64_t tmp_bytes = work_bytes - 4 * al(n * 4);
-    k_fan_keys<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(recs, n, keys_in, idx_in);
-    const hipError_t r = radix_sort(keys_in, skeys, idx_in, perm, n, 0u,
-                                    bits_for_clients(n_clients), tmp, tmp_bytes, stream);
+    k_fan_keys<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(recs, n, w.keys_in, w.idx_in);
+    const hipError_t r =
+        radix_sort(w.keys_in, w.skeys, w.idx_in, w.perm, n, 0u, bits_for_clients(n_clients),
+                   w.sort_tmp, w.sort_tmp_bytes, stream);
     if (r != hipSuccess) return r;
     const unsigned blocks = (unsigned)((n + kFanBlock - 1) / kFanBlock);
     if (((uintptr_t)out & 15) == 0)
-        k_fan_encode<true><<<blocks, kFanBlock, 0, stream>>>(recs, skeys, perm, n, n_clients, ok,
-                                                             leader, out, client_off, err);
+        k_fan_encode<true><<<blocks, kFanBlock, 0, stream>>>(recs, w.skeys, w.perm, n, n_clients,
+                                                             ok, leader, out, client_off, err);
     else
-        k_fan_encode<false><<<blocks, kFanBlock, 0, stream>>>(recs, skeys, perm, n, n_clients, ok,
-                                                              leader, out, client_off, err);
+        k_fan_encode<false><<<blocks, kFanBlock, 0, stream>>>(recs, w.skeys, w.perm, n, n_clients,
+                                                              ok, leader, out, client_off, err);
     return hipGetLastError();
 }
 

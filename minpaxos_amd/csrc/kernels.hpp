@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mpx.h"
+#include "scratch.hpp"
 
 namespace mpx {
 
@@ -125,7 +126,8 @@ struct ApplyOpts {
 // partitioned path, 48 B on the sort-based one)
 constexpr uint64_t kApplyChunkDefault = 1ull << 26;
 uint64_t apply_chunk_commands(uint64_t chunk, uint64_t m);
-uint64_t apply_work_bytes(const KvTable& t, const ApplyOpts& o, uint64_t m);
+// (a check can hand every *_work_bytes a Carver that reports the regions; scratch.hpp)
+uint64_t apply_work_bytes(const KvTable& t, const ApplyOpts& o, uint64_t m, Carver&& c = Carver());
 // a new call epoch for the table (both apply pipelines); zeroes *n_miss when given
 hipError_t launch_epoch_next(KvTable& t, uint32_t* n_miss, hipStream_t stream);
 // scratch for any call of at most max_m commands (mpx_apply_reserve)
@@ -134,19 +136,17 @@ uint64_t apply_reserve_bytes(const KvTable& t, const ApplyOpts& o, uint64_t max_
 bool apply_fast_ok(const KvTable& t);
 // the call runs the replica-batch kernels (apply_small.hip): no pipeline scratch
 bool apply_is_one_launch(const ApplyOpts& o, uint64_t m);
-uint64_t apply_fast_work_bytes(const KvTable& t, uint64_t c);
+uint64_t apply_fast_work_bytes(const KvTable& t, uint64_t n, Carver& c);
 hipError_t launch_apply_fast(KvTable& t, const uint8_t* op, const int64_t* key, const int64_t* val,
                              uint64_t m, int64_t* ret, uint8_t* conf, uint64_t C, ApplyWork& w,
                              uint32_t hot_min, uint32_t* err, hipStream_t stream);
 // replica-batch apply of at most MPX_APPLY_SMALL_MAX commands (apply_small.hip, three launches).
 // err may be a host-mapped word (the host-pointer form): the kernels raise into it with plain
-// stores (every bit they raise is kErrKvFull), never atomics. done (optional, host-mapped): the
-// last workgroup stores seq there once every result of the call is visible to the host, so the
-// host form can poll it instead of waiting on the stream
+// stores (every bit they raise is kErrKvFull), never atomics. host_io: the arrays are pinned host
+// memory, so the three-launch form (one launch would read every key over the link per workgroup)
 hipError_t launch_apply_small(KvTable& t, const uint8_t* op, const int64_t* key, const int64_t* val,
                               uint64_t m, int64_t* ret, uint8_t* conf, uint32_t* err,
-                              hipStream_t stream, uint32_t* done = nullptr, uint32_t seq = 0,
-                              bool host_io = false);
+                              hipStream_t stream, bool host_io = false);
 hipError_t launch_apply(KvTable& t, const uint8_t* op, const int64_t* key, const int64_t* val,
                         uint64_t m, int64_t* ret, uint8_t* conf, const ApplyOpts& o, ApplyWork& w,
                         uint32_t* err, hipStream_t stream);
@@ -157,7 +157,7 @@ hipError_t launch_kv_export(KvTable& t, int64_t* keys, int64_t* vals, uint64_t c
                             unsigned long long* counter, hipStream_t stream);
 
 // ---- peer stream framing (mpx_decode_peer_stream) ---------------------------------------
-uint64_t decode_work_bytes(uint64_t len);
+uint64_t decode_work_bytes(uint64_t len, Carver&& c = Carver());
 hipError_t launch_decode_peer_stream(const uint8_t* buf, uint64_t len, mpx_accept_reply* ar_out,
                                      uint64_t ar_cap, mpx_peer_frame* oth_out, uint64_t oth_cap,
                                      mpx_decode_result* res, void* work, uint64_t work_bytes,
@@ -174,14 +174,14 @@ struct StreamOuts {
     mpx_peer_frame* oth;
     uint64_t oth_cap;
 };
-uint64_t stream_work_bytes(uint64_t len);
-// frames buf[start, len) with the proto's framing; legacy = stop at variable-length messages
-hipError_t launch_decode_stream(int proto, int legacy, const uint8_t* buf, uint64_t len,
+uint64_t stream_work_bytes(uint64_t len, Carver&& c = Carver());
+// frames buf[start, len) with the proto's framing
+hipError_t launch_decode_stream(int proto, const uint8_t* buf, uint64_t len,
                                 uint64_t start, const StreamOuts& outs, mpx_stream_result* res,
                                 void* work, uint64_t work_bytes, hipStream_t stream);
 
 // ---- client reply fan-out (mpx_encode_replies) -------------------------------------------
-uint64_t fanout_work_bytes(uint64_t n);
+uint64_t fanout_work_bytes(uint64_t n, Carver&& c = Carver());
 hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t n_clients,
                                  uint8_t ok, int32_t leader, uint8_t* out, uint64_t* client_off,
                                  void* work, uint64_t work_bytes, uint32_t* err,
@@ -194,14 +194,14 @@ hipError_t launch_accept_handle(
     mpx_acceptor_state* st_out, uint64_t n_inst, int32_t base, const mpx_acceptor_group* groups,
     uint64_t n_groups, uint32_t ipg, int32_t nrep, mpx_accept_reply* replies, int32_t* reply_to,
     uint8_t* effect, uint32_t* err, hipStream_t stream);
-uint64_t accept_replies_work_bytes(uint64_t n);
+uint64_t accept_replies_work_bytes(uint64_t n, Carver&& c = Carver());
 hipError_t launch_encode_accept_replies(
     int mode, const mpx_accept_reply* replies, const int32_t* reply_to, uint64_t n,
     uint32_t n_dest, uint8_t* out, uint64_t* dest_off, void* work, uint64_t work_bytes,
     uint32_t* err, hipStream_t stream);
 
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
-uint64_t logenc_work_bytes(uint64_t n, uint64_t m);
+uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);
 hipError_t launch_encode_log(int format, const mpx_log_rec* recs, uint64_t n,
                              const uint64_t* cmd_off, const uint8_t* op, const int64_t* key,
@@ -216,6 +216,6 @@ hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_ca
                                  void* work, uint64_t work_bytes, hipStream_t stream);
 // scratch of the binned slot maximum for n records over inst_cap slots (0: the call takes the
 // per-record atomic form, which needs none)
-uint64_t replay_work_bytes(uint64_t n, int32_t inst_cap);
+uint64_t replay_work_bytes(uint64_t n, int32_t inst_cap, Carver&& c = Carver());
 
 }  // namespace mpx

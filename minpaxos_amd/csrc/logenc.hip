@@ -201,11 +201,18 @@ namespace {
 uint64_t blocks_for(uint64_t n, uint64_t m) {
     return (logenc_max_bytes(n, m) + kLogBlockBytes - 1) / kLogBlockBytes;
 }
+struct LogWork {
+    uint64_t* blk_first;  // per emit block: its first record
+    uint64_t* scan_tmp;
+    LogWork(Carver& c, uint64_t n, uint64_t m) {
+        blk_first = c.take<uint64_t>(blocks_for(n, m));
+        scan_tmp = (uint64_t*)c.take<char>(scan_scratch_bytes<uint64_t>(n ? n : 1));
+    }
+};
 }  // namespace
 
-uint64_t logenc_work_bytes(uint64_t n, uint64_t m) {
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    return al(scan_scratch_bytes<uint64_t>(n ? n : 1)) + al(blocks_for(n, m) * 8);
+uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c) {
+    return LogWork(c, n, m), c.bytes();
 }
 
 hipError_t launch_encode_log(int format, const mpx_log_rec* recs, uint64_t n,
@@ -213,20 +220,19 @@ hipError_t launch_encode_log(int format, const mpx_log_rec* recs, uint64_t n,
                              const int64_t* val, uint64_t m, uint8_t* out, uint64_t* rec_off,
                              void* work, uint64_t work_bytes, hipStream_t stream) {
     if (format != MPX_LOG_CATCHUP && format != MPX_LOG_DURABLE) return hipErrorInvalidValue;
-    if (work_bytes < logenc_work_bytes(n, m)) return hipErrorInvalidValue;
+    Carver c(work);
+    const LogWork w(c, n, m);
+    if (work_bytes < c.bytes()) return hipErrorInvalidValue;
     k_log_zero<<<1, 1, 0, stream>>>(rec_off);
     if (n == 0) return hipGetLastError();
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
     const uint64_t blocks = blocks_for(n, m);
-    uint64_t* blk_first = (uint64_t*)work;
-    uint64_t* tmp = (uint64_t*)((char*)blk_first + al(blocks * 8));
     const hipError_t r = device_scan(RecBytes{format, cmd_off},
-                                     RecOffOut{rec_off, blk_first, (uint32_t)blocks}, n,
-                                     ScanSum64{}, (uint64_t)0, tmp, stream);
+                                     RecOffOut{rec_off, w.blk_first, (uint32_t)blocks}, n,
+                                     ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
     if (r != hipSuccess) return r;
     // grid from the largest possible output (the exact size is only known on the device)
     k_log_emit<<<(unsigned)blocks, kLogBlock, 0, stream>>>(format, recs, cmd_off, op, key, val, n,
-                                                          rec_off, blk_first, (uint32_t)blocks,
+                                                          rec_off, w.blk_first, (uint32_t)blocks,
                                                           out);
     return hipGetLastError();
 }

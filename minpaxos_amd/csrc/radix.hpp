@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "scan.hpp"
+#include "scratch.hpp"
 
 namespace mpx {
 
@@ -159,37 +160,37 @@ struct RsHistOut {
     }
 };
 
-// scratch of a sort of n elements: the ping-pong keys and values, the histogram, its scan's
+// scratch of a sort of up to n elements: the ping-pong keys and values, the histogram, its scan's
 template <typename K, typename V>
-__host__ __forceinline__ uint64_t radix_scratch_bytes(uint64_t n) {
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t tiles = (n + kRsTile - 1) / kRsTile + 1;
-    const uint64_t vb = __is_same(V, RsNoValue) ? 0 : al(n * sizeof(V));
-    return al(n * sizeof(K)) + vb + al(tiles * kRsDigits * 4) +
-           al(scan_scratch_bytes<uint32_t>(tiles * kRsDigits));
+struct RadixWork {
+    K* ktmp;
+    V* vtmp = nullptr;
+    uint32_t *hist, *scan_tmp;
+    RadixWork(Carver& c, uint64_t n) {
+        const uint64_t hn = ((n + kRsTile - 1) / kRsTile + 1) * kRsDigits;
+        ktmp = c.take<K>(n);
+        if constexpr (!__is_same(V, RsNoValue)) vtmp = c.take<V>(n);
+        hist = c.take<uint32_t>(hn);
+        scan_tmp = (uint32_t*)c.take<char>(scan_scratch_bytes<uint32_t>(hn));
+    }
+};
+template <typename K, typename V>
+uint64_t radix_scratch_bytes(uint64_t n) {
+    Carver c;
+    return RadixWork<K, V>(c, n), c.bytes();
 }
 
-// sorts (kin, vin) by key bits [b0, b1) into (kout, vout), stably; n < 2^32
+// sorts (kin, vin) by key bits [b0, b1) into (kout, vout), stably; n < 2^32; scratch holds
+// scratch_bytes bytes, at least radix_scratch_bytes(n)
 template <typename K, typename V>
 hipError_t radix_sort(const K* kin, K* kout, const V* vin, V* vout, uint64_t n, unsigned b0,
                       unsigned b1, void* scratch, uint64_t scratch_bytes, hipStream_t stream) {
     if (!n) return hipSuccess;
-    if (n >= (1ull << 32) || scratch_bytes < radix_scratch_bytes<K, V>(n))
-        return hipErrorInvalidValue;
+    Carver c(scratch);
+    const RadixWork<K, V> w(c, n);
+    if (n >= (1ull << 32) || scratch_bytes < c.bytes()) return hipErrorInvalidValue;
     constexpr bool kVals = !__is_same(V, RsNoValue);
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    char* s = (char*)scratch;
-    K* ktmp = (K*)s;
-    s += al(n * sizeof(K));
-    V* vtmp = nullptr;
-    if constexpr (kVals) {
-        vtmp = (V*)s;
-        s += al(n * sizeof(V));
-    }
     const uint32_t tiles = (uint32_t)((n + kRsTile - 1) / kRsTile);
-    uint32_t* hist = (uint32_t*)s;
-    s += al(((uint64_t)tiles + 1) * kRsDigits * 4);
-    uint32_t* scan_tmp = (uint32_t*)s;
     const unsigned passes = b1 > b0 ? (b1 - b0 + 7) / 8 : 0;
     if (!passes) {  // nothing to sort on: a copy
         hipError_t r = hipMemcpyAsync(kout, kin, n * sizeof(K), hipMemcpyDeviceToDevice, stream);
@@ -202,17 +203,17 @@ hipError_t radix_sort(const K* kin, K* kout, const V* vin, V* vout, uint64_t n, 
     for (unsigned p = 0; p < passes; ++p) {
         // the last pass writes the output, the ones before alternate so that holds
         const bool to_out = ((passes - 1 - p) & 1u) == 0;
-        K* kd = to_out ? kout : ktmp;
-        V* vd = to_out ? vout : vtmp;
+        K* kd = to_out ? kout : w.ktmp;
+        V* vd = to_out ? vout : w.vtmp;
         const unsigned sh = b0 + 8 * p;
         const unsigned nb = b1 - sh < 8 ? b1 - sh : 8;
         const uint32_t mask = (1u << nb) - 1u;
-        k_rs_count<K><<<tiles, kRsT, 0, stream>>>(ks, n, sh, mask, tiles, hist);
-        const hipError_t r = device_scan(RsHistIn{hist}, RsHistOut{hist},
-                                         (uint64_t)tiles * kRsDigits, ScanSum32{}, 0u, scan_tmp,
+        k_rs_count<K><<<tiles, kRsT, 0, stream>>>(ks, n, sh, mask, tiles, w.hist);
+        const hipError_t r = device_scan(RsHistIn{w.hist}, RsHistOut{w.hist},
+                                         (uint64_t)tiles * kRsDigits, ScanSum32{}, 0u, w.scan_tmp,
                                          stream);
         if (r != hipSuccess) return r;
-        k_rs_scatter<K, V><<<tiles, kRsT, 0, stream>>>(ks, kd, vs, vd, n, sh, mask, tiles, hist);
+        k_rs_scatter<K, V><<<tiles, kRsT, 0, stream>>>(ks, kd, vs, vd, n, sh, mask, tiles, w.hist);
         ks = kd;
         vs = vd;
     }

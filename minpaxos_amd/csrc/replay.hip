@@ -64,13 +64,13 @@ constexpr int kRbPer = 16;
 constexpr uint64_t kRbChunk = kRbPer * kRbT;    // records per sort workgroup (64 KB of LDS)
 static_assert(kRbChunk <= (1u << (32 - kRbLg)), "packed pair: chunk-local index above the slot bits");
 
-// pairs: null = the atomic form, else 4 bytes per record (the u64 type is historical)
+// pairs: null = the atomic form, else 4 bytes per record
 __global__ __launch_bounds__(kReplayBlock) void k_replay_durable(
     const uint8_t* __restrict__ log, uint64_t n, int32_t inst_cap, int32_t rec_base,
     mpx_log_rec* __restrict__ recs,
     uint8_t* __restrict__ op, int64_t* __restrict__ key, int64_t* __restrict__ val,
     int32_t* __restrict__ last_rec, int32_t* __restrict__ scalars, uint32_t* __restrict__ err,
-    uint64_t* __restrict__ pairs) {
+    uint32_t* __restrict__ pairs) {
     __shared__ uint4 tile[kTileVec + 1];  // +1: the last lane's 9th dword reads past the tile
     __shared__ int32_t red[2][kReplayBlock / kWave];
     const int t = threadIdx.x;
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kReplayBlock) void k_replay_durable(
             // instanceSpace[instNo] panics outside the array (Go index check)
             const bool bad = inst < 0 || inst >= inst_cap;
             if (pairs)  // the instNo alone (~0: no slot): the record index is its place
-                st_stream(reinterpret_cast<uint32_t*>(pairs) + i, bad ? ~0u : (uint32_t)inst);
+                st_stream(pairs + i, bad ? ~0u : (uint32_t)inst);
             if (bad)
                 raise_err(err, kErrNil);
             else if (!pairs)
@@ -300,28 +300,25 @@ __global__ __launch_bounds__(kRbT) void k_rb_max_runs(const uint32_t* __restrict
     for (uint32_t j = threadIdx.x; j < ns; j += kRbT) last_rec[s0 + j] = sl[j];
 }
 
-struct RbLayout {
-    uint64_t pairs, packed, rs, total;
-};
-RbLayout rb_layout(uint64_t n, int32_t inst_cap) {
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t chunks = (n + kRbChunk - 1) / kRbChunk;
-    const uint64_t bins = ((uint64_t)inst_cap + kRbSlots - 1) / kRbSlots;
-    RbLayout L{};
-    uint64_t o = 0;
-    L.pairs = o; o += al(n * 4);  // k_replay_durable's instNos, in record order
-    L.packed = o; o += al(n * 4);
-    L.rs = o; o += al(chunks * (bins + 1) * 4);
-    L.total = o;
-    return L;
-}
 bool rb_eligible(uint64_t n, int32_t inst_cap) {
     return n > 0 && inst_cap > 0 && (int64_t)inst_cap <= kRbMaxCap && n < (1ull << 32);
 }
+struct RbWork {  // all null: no binned form for these sizes
+    uint32_t* pairs = nullptr;  // k_replay_durable's instNos, in record order
+    uint32_t *packed = nullptr, *rs = nullptr;
+    RbWork(Carver& c, uint64_t n, int32_t inst_cap) {
+        if (!rb_eligible(n, inst_cap)) return;
+        const uint64_t chunks = (n + kRbChunk - 1) / kRbChunk;
+        const uint64_t bins = ((uint64_t)inst_cap + kRbSlots - 1) / kRbSlots;
+        pairs = c.take<uint32_t>(n);
+        packed = c.take<uint32_t>(n);
+        rs = c.take<uint32_t>(chunks * (bins + 1));
+    }
+};
 }  // namespace
 
-uint64_t replay_work_bytes(uint64_t n, int32_t inst_cap) {
-    return rb_eligible(n, inst_cap) ? rb_layout(n, inst_cap).total : 0;
+uint64_t replay_work_bytes(uint64_t n, int32_t inst_cap, Carver&& c) {
+    return RbWork(c, n, inst_cap), c.bytes();
 }
 
 hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_cap,
@@ -329,23 +326,21 @@ hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_ca
                                  int32_t* last_rec, int32_t* scalars, uint32_t* err,
                                  void* work, uint64_t work_bytes, hipStream_t stream) {
     if (!n) return hipSuccess;
-    const bool binned = rb_eligible(n, inst_cap) && work &&
-                        work_bytes >= rb_layout(n, inst_cap).total;
-    const RbLayout L = binned ? rb_layout(n, inst_cap) : RbLayout{};
-    char* w = (char*)work;
-    uint64_t* pairs = binned ? (uint64_t*)(w + L.pairs) : nullptr;
+    // without the engine's scratch for this call: the atomic form
+    Carver c(work);
+    const RbWork w(c, n, inst_cap);
+    const bool binned = w.pairs && work_bytes >= c.bytes();
     // a few workgroups per CU walk the tiles (grid-stride), so the watermark atomics stay few
     const uint64_t tiles = (n + kReplayBlock - 1) / kReplayBlock;
     const uint64_t grid = tiles < kReplayGrid ? tiles : kReplayGrid;
     hipLaunchKernelGGL(k_replay_durable, dim3((unsigned)grid), dim3(kReplayBlock), 0, stream, log,
-                       n, inst_cap, rec_base, recs, op, key, val, last_rec, scalars, err, pairs);
+                       n, inst_cap, rec_base, recs, op, key, val, last_rec, scalars, err,
+                       binned ? w.pairs : nullptr);
     if (binned) {
         const uint32_t chunks = (uint32_t)((n + kRbChunk - 1) / kRbChunk);
         const uint32_t bins = (uint32_t)(((uint64_t)inst_cap + kRbSlots - 1) / kRbSlots);
-        uint32_t* packed = (uint32_t*)(w + L.packed);
-        uint32_t* rs = (uint32_t*)(w + L.rs);
-        k_rb_sort<<<chunks, kRbT, 0, stream>>>((const uint32_t*)pairs, n, bins, packed, rs);
-        k_rb_max_runs<<<bins, kRbT, 0, stream>>>(packed, rs, chunks, bins, inst_cap, rec_base,
+        k_rb_sort<<<chunks, kRbT, 0, stream>>>(w.pairs, n, bins, w.packed, w.rs);
+        k_rb_max_runs<<<bins, kRbT, 0, stream>>>(w.packed, w.rs, chunks, bins, inst_cap, rec_base,
                                                  last_rec);
     }
     return hipGetLastError();

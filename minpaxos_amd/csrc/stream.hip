@@ -1,6 +1,6 @@
 // stream.hip — full peer-stream framing: fixed AND variable-length frames, MIN or CLASSIC wire
-// (mpx_decode_stream, and mpx_decode_peer_stream as its MIN,
-// stop-at-variable special case).
+// (mpx_decode_stream. mpx_decode_peer_stream, which stops at the first
+// variable-length message, is decode.hip's).
 //
 // Reference: genericsmr.(*Replica).replicaListener src/genericsmr/genericsmr.go:402-446 reads a
 // connection as frames [code u8][body]; the body of a variable-length message (Accept, Commit,
@@ -196,10 +196,11 @@ struct SParams {
     uint64_t pos_base;   // offset of base in the caller's buffer (for record offsets)
     uint32_t entry0;     // the chain starts at base + entry0 (< 16)
     int proto;
-    int legacy;          // stop at variable-length messages (mpx_decode_peer_stream)
 };
 
 // ---- workspace ----------------------------------------------------------------------------
+uint64_t n_tiles_of(uint64_t len) { return (len + kTB - 1) / kTB; }
+
 struct Work {
     uint8_t* cmap;             // [tiles * kTL][kE] chunk maps (converged tiles skip them)
     uint8_t* tconv;            // [tiles][kTEnt] TileEnt: group 0's chunk maps, then [0] converged,
@@ -217,9 +218,25 @@ struct Work {
                                // (u8 each; k_sd_count -> k_sd_emit)
     uint64_t* stop;            // [0] stop position, [1] next, [2] reason, [3..7] VarInfo of a
                                // LONG stop frame, [8..11] the call's input counts
+    // (host) the workspace of a call on len bytes: sized for the tiles of len + 16, which covers
+    // the launch's n_tiles_of(P.len + 1) for every start
+    Work(Carver& c, uint64_t len) {
+        const uint64_t tiles = n_tiles_of(len + 16), groups = (tiles + kGT - 1) / kGT;
+        cmap = c.take<uint8_t>(tiles * kTL * kE);
+        tconv = c.take<uint8_t>(tiles * kTEnt);
+        tmap = c.take<uint8_t>(tiles * kE);
+        tent = c.take<uint8_t>(tiles);
+        gmap = c.take<uint8_t>(groups * kE);
+        gent = c.take<uint8_t>(groups);
+        tcnt = c.take<uint32_t>(tiles * 4);
+        tpre = c.take<uint32_t>(tiles * 4);
+        btot = c.take<uint32_t>((tiles / 1024 + 1) * 4);
+        boff = c.take<uint32_t>((tiles / 1024 + 1) * 4);
+        ticket = c.take<uint32_t>(1);
+        cinfo = c.take<uint2>(tiles * kTL);
+        stop = c.take<uint64_t>(12);
+    }
 };
-
-uint64_t n_tiles_of(uint64_t len) { return (len + kTB - 1) / kTB; }
 
 }  // namespace
 
@@ -324,8 +341,8 @@ __host__ __device__ __forceinline__ uint32_t var_land(const ByteAt& R, uint32_t 
 // Phase 2a' (a chunk holding a variable-message code byte - any byte 9, 10 or 12, at the
 // positions of other frames' payload too: ~12 per 64 chunks of the bench's MIN stream, runs of
 // ~9 per chunk where an instance number has such a byte): the bounded parse of each, D[p] = the
-// frame's landing, or 0xFF: a terminal (unparseable, landing kE or more bytes into the next
-// chunk, or legacy mode, which stops at every variable-length message).
+// frame's landing, or 0xFF: a terminal (unparseable, or landing kE or more bytes into the next
+// chunk).
 // The wave's positions are one task list: each lane's positions were its own serial loop, so a
 // wave took as many rounds as its busiest lane, each as long as its deepest parse (catch-up
 // logs over zero-rich payload: ~20 dependent reads). Tasks (lane << 7 | position, u16) go to
@@ -386,7 +403,7 @@ __device__ __forceinline__ uint32_t var_wave(const SParams P, uint64_t t0, uint6
 #pragma unroll 1
         for (uint32_t j = ln; j < ((n + 63u) & ~63u); j += 64) {
             uint32_t v = 0xFFu;
-            if (j < n && !P.legacy) {
+            if (j < n) {
                 const uint32_t tk = T[j], src = w0 + (tk >> 7), p = tk & 127u;
                 const uint64_t cs = t0 + (uint64_t)src * kC;
                 const uint32_t e = (uint32_t)min(P.len - cs, (uint64_t)(kC + kE - 1));
@@ -802,8 +819,8 @@ __device__ __forceinline__ void first_terminal(const uint8_t (*S)[kE], uint32_t 
 }
 // The position in the chunk at c0 where the chain entering at e reaches its terminal, by the
 // rules k_sd_tile_maps' DP applies (the chunk maps store a terminal without its position): the
-// end of the buffer, a frame past it, a legacy-mode or unparseable variable-length message, or
-// one landing kE or more bytes into the next chunk. Thread 0 of the walk, once per call.
+// end of the buffer, a frame past it, an unparseable variable-length message, or one landing kE
+// or more bytes into the next chunk. Thread 0 of the walk, once per call.
 __device__ uint32_t chunk_terminal(const SParams& P, uint64_t c0, uint32_t e) {
     const Bytes by{P.buf, nullptr, 0, 0};
     uint32_t p = e;
@@ -813,7 +830,6 @@ __device__ uint32_t chunk_terminal(const SParams& P, uint64_t c0, uint32_t e) {
         const uint32_t code = P.buf[a];
         uint32_t fl = flen(code, P.proto);
         if (!fl) {
-            if (P.legacy) return p;
             const VarRes r = parse_var(by, P.len, c0 + kC + kE - 1, a, P.proto);
             if (r.st != kOk || p + r.f.len >= (uint32_t)(kC + kE)) return p;
             fl = r.f.len;
@@ -940,8 +956,6 @@ __global__ __launch_bounds__(kParts * kE) void k_sd_walk(SParams P, Work W, uint
             const uint32_t fl = flen((uint32_t)code, P.proto);
             if (fl) {
                 why = MPX_DECODE_PARTIAL;  // a fixed frame past the end (the only fixed terminal)
-            } else if (P.legacy) {
-                why = MPX_DECODE_VARIABLE;
             } else {
                 const VarRes r = parse_var(Bytes{P.buf, nullptr, 0, 0}, P.len, ~0ull, s, P.proto);
                 why = r.st == kOk ? MPX_DECODE_LONG : r.st == kPartial ? MPX_DECODE_PARTIAL
@@ -1572,57 +1586,26 @@ __global__ void k_sd_empty(mpx_stream_result* res, uint64_t at) {
 }
 
 // ---- host side ----------------------------------------------------------------------------
-namespace {
-struct Layout {
-    uint64_t cmap, tconv, tmap, tent, gmap, gent, tcnt, tpre, btot, boff, ticket, cinfo, stop, total;
-};
-Layout layout_of(uint64_t len) {
-    const uint64_t tiles = n_tiles_of(len + 16), groups = (tiles + kGT - 1) / kGT;
-    auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-    Layout L{};
-    uint64_t o = 0;
-    L.cmap = o; o += al(tiles * kTL * kE);
-    L.tconv = o; o += al(tiles * kTEnt);
-    L.tmap = o; o += al(tiles * kE);
-    L.tent = o; o += al(tiles);
-    L.gmap = o; o += al(groups * kE);
-    L.gent = o; o += al(groups);
-    L.tcnt = o; o += al(tiles * 16);
-    L.tpre = o; o += al(tiles * 16);
-    L.btot = o; o += al((tiles / 1024 + 1) * 16);
-    L.boff = o; o += al((tiles / 1024 + 1) * 16);
-    L.ticket = o; o += al(4);
-    L.cinfo = o; o += al(tiles * kTL * 8);
-    L.stop = o; o += al(12 * 8);
-    L.total = o;
-    return L;
-}
-}  // namespace
+uint64_t stream_work_bytes(uint64_t len, Carver&& c) { return Work(c, len), c.bytes(); }
 
-uint64_t stream_work_bytes(uint64_t len) { return layout_of(len).total; }
-
-hipError_t launch_decode_stream(int proto, int legacy, const uint8_t* buf, uint64_t len,
+hipError_t launch_decode_stream(int proto, const uint8_t* buf, uint64_t len,
                                 uint64_t start, const StreamOuts& outs, mpx_stream_result* res,
                                 void* work, uint64_t work_bytes, hipStream_t stream) {
     if (len > (uint64_t)MPX_DECODE_MAX_BYTES || start > len) return hipErrorInvalidValue;
-    if (work_bytes < stream_work_bytes(len)) return hipErrorInvalidValue;
+    Carver c(work);
+    const Work W(c, len);
+    if (work_bytes < c.bytes()) return hipErrorInvalidValue;
     if (start == len) {
         k_sd_empty<<<1, 1, 0, stream>>>(res, start);
         return hipGetLastError();
     }
     const uint64_t base = start & ~15ull;
-    SParams P{buf + base, len - base, base, (uint32_t)(start - base), proto, legacy};
+    SParams P{buf + base, len - base, base, (uint32_t)(start - base), proto};
     // one tile more when len is a multiple of the tile: position len is a terminal the chain
     // must be able to land on
     const uint32_t tiles = (uint32_t)n_tiles_of(P.len + 1);
     const uint32_t groups = (tiles + kGT - 1) / kGT;
-    const Layout L = layout_of(len);
-    char* w = (char*)work;
-    Work W{(uint8_t*)(w + L.cmap), (uint8_t*)(w + L.tconv), (uint8_t*)(w + L.tmap), (uint8_t*)(w + L.tent),
-           (uint8_t*)(w + L.gmap), (uint8_t*)(w + L.gent), (uint32_t*)(w + L.tcnt),
-           (uint32_t*)(w + L.tpre), (uint32_t*)(w + L.btot), (uint32_t*)(w + L.boff),
-           (uint32_t*)(w + L.ticket), (uint2*)(w + L.cinfo), (uint64_t*)(w + L.stop)};
-    const hipError_t r = hipMemsetAsync(w + L.ticket, 0, 4, stream);
+    const hipError_t r = hipMemsetAsync(W.ticket, 0, 4, stream);
     if (r != hipSuccess) return r;
     Outs O{outs.ar, outs.ar_cap, outs.prep, outs.prep_cap, outs.var, outs.var_cap, outs.oth,
            outs.oth_cap};

@@ -409,7 +409,9 @@ uint64_t apply_chunk_commands(uint64_t c, uint64_t m) { return c ? c : m; }
 bool apply_is_one_launch(const ApplyOpts& o, uint64_t m) {
     return m && m <= MPX_APPLY_SMALL_MAX && (o.path == MPX_APPLY_AUTO || o.path == MPX_APPLY_SMALL);
 }
-uint64_t apply_work_bytes(const KvTable&, const ApplyOpts&, uint64_t m) { return 48 * m + 256; }
+uint64_t apply_work_bytes(const KvTable&, const ApplyOpts&, uint64_t m, Carver&&) {
+    return 48 * m + 256;
+}
 uint64_t apply_reserve_bytes(const KvTable&, const ApplyOpts&, uint64_t m) { return 48 * m + 256; }
 hipError_t launch_apply(KvTable&, const uint8_t* op, const int64_t* key, const int64_t* val,
                         uint64_t m, int64_t* ret, uint8_t* conf, const ApplyOpts&, ApplyWork& w,
@@ -424,9 +426,7 @@ hipError_t launch_apply(KvTable&, const uint8_t* op, const int64_t* key, const i
 }
 // the replica-batch form: nothing to compute on the stub, but the call completes (its flag)
 hipError_t launch_apply_small(KvTable&, const uint8_t*, const int64_t*, const int64_t*, uint64_t,
-                              int64_t*, uint8_t*, uint32_t*, hipStream_t, uint32_t* done,
-                              uint32_t seq, bool) {
-    if (done) *done = seq;
+                              int64_t*, uint8_t*, uint32_t*, hipStream_t, bool) {
     return hipSuccess;
 }
 hipError_t launch_kv_clear(KvTable&, hipStream_t) { return hipSuccess; }
@@ -442,7 +442,7 @@ hipError_t launch_kv_export(KvTable&, int64_t* keys, int64_t* vals, uint64_t cap
     fill(vals, cap * 8, 1);
     return hipSuccess;
 }
-uint64_t decode_work_bytes(uint64_t len) { return len / 8 + 256; }
+uint64_t decode_work_bytes(uint64_t len, Carver&&) { return len / 8 + 256; }
 hipError_t launch_decode_peer_stream(const uint8_t* buf, uint64_t len, mpx_accept_reply* ar,
                                      uint64_t ar_cap, mpx_peer_frame* oth, uint64_t oth_cap,
                                      mpx_decode_result* res, void* work, uint64_t work_bytes,
@@ -454,8 +454,8 @@ hipError_t launch_decode_peer_stream(const uint8_t* buf, uint64_t len, mpx_accep
     scratch(work, work_bytes);
     return hipSuccess;
 }
-uint64_t stream_work_bytes(uint64_t len) { return len + 256; }
-hipError_t launch_decode_stream(int proto, int, const uint8_t* buf, uint64_t len, uint64_t,
+uint64_t stream_work_bytes(uint64_t len, Carver&&) { return len + 256; }
+hipError_t launch_decode_stream(int proto, const uint8_t* buf, uint64_t len, uint64_t,
                                 const StreamOuts& o, mpx_stream_result* res, void* work,
                                 uint64_t work_bytes, hipStream_t) {
     touch(buf, len);
@@ -469,7 +469,7 @@ hipError_t launch_decode_stream(int proto, int, const uint8_t* buf, uint64_t len
     scratch(work, work_bytes);
     return hipSuccess;
 }
-uint64_t fanout_work_bytes(uint64_t n) { return 8 * n + 256; }
+uint64_t fanout_work_bytes(uint64_t n, Carver&&) { return 8 * n + 256; }
 hipError_t launch_encode_replies(const mpx_reply_rec* recs, uint64_t n, uint32_t n_clients, uint8_t,
                                  int32_t, uint8_t* out, uint64_t* client_off, void* work,
                                  uint64_t work_bytes, uint32_t*, hipStream_t) {
@@ -492,7 +492,7 @@ hipError_t launch_accept_handle(int, const mpx_accept_msg* msgs, uint64_t n,
     fill(effect, n, 2);
     return hipSuccess;
 }
-uint64_t accept_replies_work_bytes(uint64_t n) { return 4 * n + 256; }
+uint64_t accept_replies_work_bytes(uint64_t n, Carver&&) { return 4 * n + 256; }
 // dest_off: n frames split evenly over the destinations
 hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replies,
                                         const int32_t* reply_to, uint64_t n, uint32_t n_dest,
@@ -507,7 +507,7 @@ hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replie
     if (n) scratch(work, work_bytes);
     return hipSuccess;
 }
-uint64_t logenc_work_bytes(uint64_t n, uint64_t) { return 8 * n + 256; }
+uint64_t logenc_work_bytes(uint64_t n, uint64_t, Carver&&) { return 8 * n + 256; }
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m) { return 18 * n + 17 * m; }
 // rec_off: 18 bytes per record and 17 per command, as the bound above
 hipError_t launch_encode_log(int, const mpx_log_rec* recs, uint64_t n, const uint64_t* cmd_off,
@@ -540,5 +540,5 @@ hipError_t launch_replay_durable(const uint8_t* log, uint64_t n, int32_t inst_ca
     scratch(work, work_bytes);
     return hipSuccess;
 }
-uint64_t replay_work_bytes(uint64_t n, int32_t) { return 16 * n + 256; }
+uint64_t replay_work_bytes(uint64_t n, int32_t, Carver&&) { return 16 * n + 256; }
 }  // namespace mpx
