@@ -33,6 +33,10 @@
  *                            paxos.(*Replica).handleAccept  src/paxos/paxos.go:470-520: the
  *                            acceptor's half of Phase 2, and mpx_encode_accept_replies the
  *                            AcceptReply frames replyAccept writes to each leader's connection
+ *   mpx_propose_handle    <- bareminpaxos.(*Replica).handlePropose  bareminpaxos.go:617-710 /
+ *                            paxos.(*Replica).handlePropose  src/paxos/paxos.go:388-443: which
+ *                            drained proposals become an instance, and mpx_encode_accepts the
+ *                            Accept frames bcastAccept (:450-520 / :299-331) writes to every peer
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -88,7 +92,8 @@ extern "C" {
 #define MPX_ABI_VERSION 8  /* 4: + mpx_group_step_totals_dev; 5: + mpx_graph_*, mpx_apply_buffers / _staged;
                               6: + mpx_replay_durable_reserve; 7: + mpx_group_step_events;
                               8: + MPX_FLAG_STEP_ONE_LAUNCH; additive since, same number:
-                              mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev] */
+                              mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev],
+                              mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -746,6 +751,142 @@ int mpx_encode_log_dev(mpx_engine* eng, int format, const mpx_log_rec* d_recs, s
                        const uint64_t* d_cmd_off, const uint8_t* d_op, const int64_t* d_key,
                        const int64_t* d_val, size_t m, uint8_t* d_out, uint64_t* d_rec_off,
                        void* stream);
+
+/* ---- the proposer side: batched handlePropose and the Accept bytes --------------------------
+ * The first two stations of Phase 2:
+ *   handlePropose  bareminpaxos.go:617-710 (MIN) / paxos.go:388-443 (CLASSIC)
+ *   bcastAccept    bareminpaxos.go:450-520 / paxos.go:299-331, through SendMsg
+ *                  (genericsmr.go:499-512) and Accept.Marshal (minpaxosprotomarsh.go:425-468 /
+ *                  paxosprotomarsh.go:214-242)
+ * Instance numbers are window numbers as in mpx_accept_handle: idx = instance - inst_base belongs
+ * to group g = idx / ipg, n_inst == n_groups * ipg, first_g = inst_base + g * ipg plays the
+ * reference's instance 0 of group g and "nothing committed" is first_g - 1.                     */
+
+/* per group: r.defaultBallot, r.Id, r.Leader (CLASSIC: IsLeader is leader == self_id),
+ * prepareBookkeeping.prepareOKs (MIN), r.crtInstance (in/out), r.committedUpTo                  */
+typedef struct mpx_proposer_group {
+    int32_t default_ballot;
+    int32_t self_id;
+    int32_t leader;
+    int32_t prepare_oks;
+    int32_t crt_instance;
+    int32_t committed_upto;
+    uint32_t pad[2];
+} mpx_proposer_group; /* 32 B */
+
+/* one run of handlePropose: a batch of at most MPX_PROPOSE_MAX_BATCH proposals and what became
+ * of it. first_cmd / n_cmds: the batch's range of the call's proposal (= command) arrays.       */
+typedef struct mpx_accept_send {
+    int32_t instance;       /* instNo (ACCEPT, PREPARE, REFUSED), else -1                       */
+    int32_t ballot;         /* the installed ballot (REFUSED: defaultBallot)                    */
+    int32_t last_committed; /* r.committedUpTo, bcastAccept's lastcommitted                     */
+    uint32_t flags;         /* MPX_PH_*                                                         */
+    uint64_t first_cmd;
+    uint32_t n_cmds;
+    uint32_t pad;
+} mpx_accept_send; /* 32 B */
+
+#define MPX_PROPOSE_MAX_BATCH 5000 /* MAX_BATCH, bareminpaxos.go:22 / paxos.go:20               */
+#define MPX_PH_ACCEPT 1u     /* instance installed PREPARED at defaultBallot: bcastAccept (after
+                                recordInstanceMetadata + recordCommands + sync)                 */
+#define MPX_PH_NOT_LEADER 2u /* every proposal of the slot is answered FALSE                    */
+#define MPX_PH_REFUSED 4u    /* MIN :671-685: the batch is consumed, its FIRST proposal is
+                                answered FALSE, the others get no reply                         */
+#define MPX_PH_PREPARE 8u    /* CLASSIC :421-428: installed PREPARING at makeUniqueBallot(0) =
+                                self_id; the host does bcastPrepare                             */
+
+/* Group g's drained proposals are [prop_off[g], prop_off[g+1]) of the call's proposal arrays, in
+ * arrival order (only the counts enter this call). The handler runs once per MPX_PROPOSE_MAX_BATCH
+ * of them, sequentially: slot send_off[g] + b describes proposals [prop_off[g] + 5000 b, ...) and
+ * send_off[g+1] - send_off[g] = ceil(n_g / 5000). Every slot is written; there is no compaction.
+ *   both     not leader (MIN: also prepare_oks <= N>>1): MPX_PH_NOT_LEADER on every slot of the
+ *            group, nothing else changes
+ *   MIN      crt_instance advances past non-nil slots, instNo = crt; committed_upto < instNo-1 ->
+ *            MPX_PH_REFUSED (crt stays advanced); else crt++, st[instNo] = {PREPARED,
+ *            default_ballot, value_id = (uint32) first_cmd, MPX_PF_HAS_PROPOSALS}, MPX_PH_ACCEPT
+ *            with {instNo, default_ballot, committed_upto}
+ *   CLASSIC  advance, instNo = crt, crt++ (no pipeline check); default_ballot == -1 ->
+ *            {PREPARING, self_id, ...} and MPX_PH_PREPARE, else {PREPARED, default_ballot, ...}
+ *            and MPX_PH_ACCEPT
+ * lb (optional): installed instances get {status, 0, 0, 0}, so mpx_accept_tally can run on it.
+ * crt_instance leaving the group's window [first_g, first_g + ipg) is the reference's
+ * instanceSpace index panic: MPX_E_NIL_INSTANCE, outputs unspecified.
+ * Host form: computes send_off (n_groups+1 entries, always written once the arguments are valid);
+ * MPX_E_INVAL when prop_off decreases or send_off[n_groups] > sends_cap.                        */
+int mpx_propose_handle(mpx_engine* eng, mpx_proposer_group* groups, size_t n_groups,
+                       const uint64_t* prop_off, mpx_acceptor_state* st, mpx_inst_state* lb,
+                       size_t n_inst, int32_t inst_base, uint32_t ipg, uint64_t* send_off,
+                       mpx_accept_send* sends, size_t sends_cap);
+/* device form: d_send_off is an input, trusted like d_prop_off. One kernel, a lane per group, no
+ * scratch, no control words beyond the error word; it captures into a graph.                   */
+int mpx_propose_handle_dev(mpx_engine* eng, mpx_proposer_group* d_groups, size_t n_groups,
+                           const uint64_t* d_prop_off, const uint64_t* d_send_off,
+                           mpx_acceptor_state* d_st, mpx_inst_state* d_lb, size_t n_inst,
+                           int32_t inst_base, uint32_t ipg, mpx_accept_send* d_sends,
+                           void* stream);
+
+#define MPX_AB_THRIFTY 1u /* r.Thrifty: N>>1 destinations instead of N-1                         */
+
+/* one call of mpx_encode_accepts. Slots of sends without MPX_PH_ACCEPT are skipped.
+ * groups: self_id is LeaderId (the other fields are not read). peer_commits[n_groups * N]:
+ * prepareBookkeeping.peerCommits per group (MIN). cmd_*: the new commands, SoA, indexed by a
+ * send's first_cmd / n_cmds. The log, by window index (MIN): log_recs[n_inst] (ballot, status;
+ * MPX_STATUS_NIL = nil; inst_no unused) with commands [log_cmd_off[i], log_cmd_off[i+1]) of
+ * log_op / log_key / log_val. alive_mask: bit q = r.Alive[q] (CLASSIC).                        */
+typedef struct mpx_accept_batch {
+    const mpx_accept_send* sends;
+    size_t n_sends;
+    int32_t inst_base;
+    uint32_t ipg;
+    size_t n_groups;
+    const mpx_proposer_group* groups;
+    const int32_t* peer_commits;
+    const uint8_t* cmd_op;
+    const int64_t* cmd_key;
+    const int64_t* cmd_val;
+    size_t n_cmds;
+    const mpx_log_rec* log_recs;
+    const uint64_t* log_cmd_off;
+    const uint8_t* log_op;
+    const int64_t* log_key;
+    const int64_t* log_val;
+    size_t n_log_cmds;
+    uint32_t flags;      /* MPX_AB_*                                                            */
+    uint32_t alive_mask;
+} mpx_accept_batch;
+
+/* Destinations of a send, in ring order q = self_id+1, ... mod N up to self_id; n = N-1, or N>>1
+ * with MPX_AB_THRIFTY. MIN: the first n successors, alive or not (the reference reconnects and
+ * counts the peer, :476-482). CLASSIC: the first n successors whose alive bit is set (:323-327).
+ * Frames, little endian, V = binary.PutVarint:
+ *   MIN      [9][LeaderId][Instance][Ballot][LastCommitted][V(n)][n x 17 B][V(m)][m Instances]
+ *            peer q's CatchUpLog: instances lo .. last_committed of the group's log, lo = first_g
+ *            if peer_commits[q] < first_g, else peer_commits[q] + 1 (:496-506); empty when
+ *            lo > last_committed. Instance = Ballot i32, Status i32, V(k), k x 17 B.
+ *   CLASSIC  [9][LeaderId][Instance][Ballot][V(n)][n x 17 B]
+ * out receives, destination by destination, each destination's frames in send-array order, back
+ * to back; destination q's run is out[dest_off[q] .. dest_off[q+1]) (dest_off: N+1 entries,
+ * always complete). Nothing is ever written at or past out_cap.
+ * Errors: a nil instance inside a catch-up range (the reference dereferences nil) ->
+ * MPX_E_NIL_INSTANCE. Host form: last_committed >= instance or < first_g - 1, a send outside the
+ * window, a command or log range outside its arrays, self_id outside [0, N) -> MPX_E_INVAL;
+ * dest_off[N] > out_cap -> MPX_E_INVAL with dest_off written.                                  */
+int mpx_encode_accepts(mpx_engine* eng, const mpx_accept_batch* b, uint8_t* out, size_t out_cap,
+                       uint64_t* dest_off);
+/* scratch for _dev calls of up to max_sends slots over a window of up to max_n_inst instances
+ * (max_log_cmds: reserved for forms that materialise the catch-up runs; the built one keeps only
+ * offsets). Grows only. The scratch lives in the handle: like the other *_dev calls that keep
+ * scratch there, encodes of one handle run in one stream order, and a larger reserve invalidates
+ * graphs captured before it.                                                                    */
+int mpx_encode_accepts_reserve(mpx_engine* eng, size_t max_sends, size_t max_n_inst,
+                               size_t max_log_cmds);
+/* b: a host struct of device pointers. The offsets and ranges are trusted; a send outside the
+ * window (MPX_E_NIL_INSTANCE), a bad self_id (MPX_E_BAD_ID) or last_committed (MPX_E_INVAL) is
+ * reported through the error word like the other _dev calls and emits no frame. Never allocates
+ * or synchronises. Alignment: sends, groups, log_recs 16 bytes; offsets, keys, values 8;
+ * cmd_op, log_op and d_out any address.                                                         */
+int mpx_encode_accepts_dev(mpx_engine* eng, const mpx_accept_batch* b, uint8_t* d_out,
+                           size_t out_cap, uint64_t* d_dest_off, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

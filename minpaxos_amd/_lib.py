@@ -37,6 +37,14 @@ class MpxDecodeOut(C.Structure):
                 ("var_cap", _sz), ("other", _p), ("other_cap", _sz)]
 
 
+class MpxAcceptBatch(C.Structure):
+    _fields_ = [("sends", _p), ("n_sends", _sz), ("inst_base", C.c_int32), ("ipg", C.c_uint32),
+                ("n_groups", _sz), ("groups", _p), ("peer_commits", _p), ("cmd_op", _p),
+                ("cmd_key", _p), ("cmd_val", _p), ("n_cmds", _sz), ("log_recs", _p),
+                ("log_cmd_off", _p), ("log_op", _p), ("log_key", _p), ("log_val", _p),
+                ("n_log_cmds", _sz), ("flags", C.c_uint32), ("alive_mask", C.c_uint32)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -88,6 +96,12 @@ SIGNATURES = {
     "mpx_encode_accept_replies": (C.c_int, [_p, _p, _p, _sz, C.c_uint32, _p, _p]),
     "mpx_encode_accept_replies_reserve": (C.c_int, [_p, _sz]),
     "mpx_encode_accept_replies_dev": (C.c_int, [_p, _p, _p, _sz, C.c_uint32, _p, _p, _p]),
+    "mpx_propose_handle": (C.c_int, [_p, _p, _sz, _p, _p, _p, _sz, _i32, C.c_uint32, _p, _p, _sz]),
+    "mpx_propose_handle_dev": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _sz, _i32, C.c_uint32, _p,
+                                         _p]),
+    "mpx_encode_accepts": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p]),
+    "mpx_encode_accepts_reserve": (C.c_int, [_p, _sz, _sz, _sz]),
+    "mpx_encode_accepts_dev": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

@@ -72,7 +72,7 @@ struct mpx_engine {
     mpx::KvTable kv{};
     bool kv_ready = false;
     // the families' scratch: grown by the host forms and the *_reserve calls, never by a _dev form
-    DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work;
+    DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work, ab_work;
     mpx::ApplyOpts apply{};  // mpx_config.apply_* (fixed for the handle's life)
     // replica-sized mpx_apply calls: pinned, GPU-mapped staging the one-launch kernel reads the
     // commands from and writes the results to (no DMA copies on the call's path)
@@ -389,7 +389,7 @@ int mpx_close(mpx_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->comm) ncclCommDestroy(e->comm);
     for (DevBuf* x : {&e->arena, &e->apply_work, &e->decode_work, &e->stream_work, &e->fan_work,
-                      &e->log_work, &e->replay_work, &e->are_work, &e->worklist})
+                      &e->log_work, &e->replay_work, &e->are_work, &e->ab_work, &e->worklist})
         if (x->p) (void)hipFree(x->p);
     if (e->pin_io.p) (void)hipHostFree(e->pin_io.p);
     if (e->pin_staged.p) (void)hipHostFree(e->pin_staged.p);
@@ -1310,6 +1310,248 @@ int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
     CK(L.out(s_out, out, total));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return MPX_OK;
+}
+
+// ---- the proposer side: handlePropose and the Accept bytes -----------------------------------
+// (the launchers are weak: a build without proposer.hip validates and then answers
+// MPX_E_UNSUPPORTED)
+namespace {
+const char* const kNoProposer = "the proposer kernels are not built in";
+
+int propose_shape(mpx_engine* e, size_t n_groups, size_t n_inst, uint32_t ipg) {
+    if (n_groups > (1ull << 32) || n_inst > (1ull << 32) ||
+        (n_groups ? (!ipg || n_groups * (uint64_t)ipg != n_inst) : n_inst != 0))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    return MPX_OK;
+}
+
+// bcastAccept's ring walk from self (bareminpaxos.go:465-482 / paxos.go:312-327): bit q set when
+// q receives the Accept
+uint32_t accept_dests(int mode, int32_t N, int32_t self, bool thrifty, uint32_t alive) {
+    const int n = thrifty ? N >> 1 : N - 1;
+    uint32_t m = 0;
+    int32_t q = self;
+    for (int sent = 0; sent < n;) {
+        q = (q + 1) % N;
+        if (q == self) break;
+        if (mode != MPX_MODE_MIN && !((alive >> q) & 1u)) continue;
+        ++sent;
+        m |= 1u << q;
+    }
+    return m;
+}
+}  // namespace
+
+int mpx_propose_handle_dev(mpx_engine* e, mpx_proposer_group* d_groups, size_t n_groups,
+                           const uint64_t* d_prop_off, const uint64_t* d_send_off,
+                           mpx_acceptor_state* d_st, mpx_inst_state* d_lb, size_t n_inst,
+                           int32_t inst_base, uint32_t ipg, mpx_accept_send* d_sends,
+                           void* stream) {
+    if (!e) return MPX_E_INVAL;
+    if (n_groups && (!d_groups || !d_prop_off || !d_send_off || !d_st || !d_sends))
+        return fail(e, MPX_E_INVAL, "null argument");
+    CK(propose_shape(e, n_groups, n_inst, ipg));
+    if (!mpx::launch_propose_handle)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_propose_handle: ") + kNoProposer);
+    HIPCHK(e, mpx::launch_propose_handle(e->cfg.mode, d_groups, n_groups, d_prop_off, d_send_off,
+                                         d_st, d_lb, n_inst, inst_base, ipg, e->cfg.n_replicas,
+                                         d_sends, e->d_err, pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_propose_handle(mpx_engine* e, mpx_proposer_group* groups, size_t n_groups,
+                       const uint64_t* prop_off, mpx_acceptor_state* st, mpx_inst_state* lb,
+                       size_t n_inst, int32_t inst_base, uint32_t ipg, uint64_t* send_off,
+                       mpx_accept_send* sends, size_t sends_cap) {
+    if (!e) return MPX_E_INVAL;
+    if (!send_off || (n_groups && (!groups || !prop_off || !st)))
+        return fail(e, MPX_E_INVAL, "null argument");
+    CK(propose_shape(e, n_groups, n_inst, ipg));
+    send_off[0] = 0;
+    for (size_t g = 0; g < n_groups; ++g) {
+        if (prop_off[g] > prop_off[g + 1])
+            return fail(e, MPX_E_INVAL, "prop_off must be non-decreasing");
+        const uint64_t n_g = prop_off[g + 1] - prop_off[g];
+        send_off[g + 1] = send_off[g] + (n_g + MPX_PROPOSE_MAX_BATCH - 1) / MPX_PROPOSE_MAX_BATCH;
+    }
+    const uint64_t n_sends = send_off[n_groups];
+    if (n_sends > sends_cap || (n_sends && !sends))
+        return fail(e, MPX_E_INVAL, "sends_cap is smaller than send_off[n_groups]");
+    const int32_t N = e->cfg.n_replicas;
+    for (size_t g = 0; g < n_groups; ++g) {  // a leader whose crtInstance is outside its window
+        const mpx_proposer_group& G = groups[g];
+        const bool leads = G.leader == G.self_id &&
+                           (e->cfg.mode != MPX_MODE_MIN || G.prepare_oks > (N >> 1));
+        const int64_t first = (int64_t)inst_base + (int64_t)g * ipg;
+        if (leads && prop_off[g + 1] > prop_off[g] &&
+            (G.crt_instance < first || G.crt_instance >= first + (int64_t)ipg))
+            return fail(e, MPX_E_NIL_INSTANCE, "crt_instance is outside its group's window");
+    }
+    if (!mpx::launch_propose_handle)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_propose_handle: ") + kNoProposer);
+    CK(begin(e));
+    Stage L(e);
+    const Slot s_grp = L.add(n_groups * sizeof(mpx_proposer_group)),
+               s_poff = L.add(n_groups ? (n_groups + 1) * 8 : 0),
+               s_soff = L.add(n_groups ? (n_groups + 1) * 8 : 0),
+               s_st = L.add(n_inst * sizeof(mpx_acceptor_state)),
+               s_lb = L.add(lb ? n_inst * sizeof(mpx_inst_state) : 0),
+               s_snd = L.add(n_sends * sizeof(mpx_accept_send));
+    CK(L.commit());
+    CK(L.in(s_grp, groups));
+    CK(L.in(s_poff, prop_off));
+    CK(L.in(s_soff, send_off));
+    CK(L.in(s_st, st));
+    if (lb) CK(L.in(s_lb, lb));
+    CK(mpx_propose_handle_dev(e, L.at<mpx_proposer_group>(s_grp), n_groups,
+                              L.at<uint64_t>(s_poff), L.at<uint64_t>(s_soff),
+                              L.at<mpx_acceptor_state>(s_st), L.at<mpx_inst_state>(s_lb, lb),
+                              n_inst, inst_base, ipg, L.at<mpx_accept_send>(s_snd), e->stream));
+    CK(L.out(s_grp, groups));
+    CK(L.out(s_st, st));
+    if (lb) CK(L.out(s_lb, lb));
+    CK(L.out(s_snd, sends));
+    return finish(e);
+}
+
+int mpx_encode_accepts_reserve(mpx_engine* e, size_t max_sends, size_t max_n_inst,
+                               size_t max_log_cmds) {
+    if (!e) return MPX_E_INVAL;
+    (void)max_log_cmds;  // (the built form keeps offsets only, no catch-up bytes)
+    if (max_sends >= (1ull << 32) || max_n_inst > (1ull << 32))
+        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends over 2^32 instances per call");
+    if (!mpx::accepts_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
+    return reserve(e, e->ab_work,
+                   mpx::accepts_work_bytes((uint32_t)e->cfg.n_replicas, max_sends, max_n_inst));
+}
+
+int mpx_encode_accepts_dev(mpx_engine* e, const mpx_accept_batch* b, uint8_t* d_out,
+                           size_t out_cap, uint64_t* d_dest_off, void* stream) {
+    if (!e) return MPX_E_INVAL;
+    if (!b || !d_dest_off || (out_cap && !d_out) || (b->n_sends && (!b->sends || !b->groups)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    const size_t n_inst = b->n_groups * (size_t)b->ipg;
+    CK(propose_shape(e, b->n_groups, n_inst, b->ipg));
+    if (b->n_sends >= (1ull << 32))
+        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends per call");
+    if (b->n_sends && !b->n_groups) return fail(e, MPX_E_INVAL, "sends without a window");
+    if (e->cfg.mode == MPX_MODE_MIN && b->n_sends &&
+        (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
+        return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
+    if (!mpx::launch_encode_accepts || !mpx::accepts_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
+    // (an empty call uses no scratch)
+    CK(reserved(e, e->ab_work,
+                b->n_sends ? mpx::accepts_work_bytes((uint32_t)e->cfg.n_replicas, b->n_sends, n_inst)
+                           : 0,
+                "mpx_encode_accepts_dev", "mpx_encode_accepts_reserve(n_sends, n_inst, m)"));
+    HIPCHK(e, mpx::launch_encode_accepts(e->cfg.mode, e->cfg.n_replicas, b, d_out, out_cap,
+                                         d_dest_off, e->ab_work.p, e->ab_work.cap, e->d_err,
+                                         pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_encode_accepts(mpx_engine* e, const mpx_accept_batch* b, uint8_t* out, size_t out_cap,
+                       uint64_t* dest_off) {
+    if (!e) return MPX_E_INVAL;
+    if (!b || !dest_off || (out_cap && !out) || (b->n_sends && (!b->sends || !b->groups)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    const size_t n_inst = b->n_groups * (size_t)b->ipg;
+    CK(propose_shape(e, b->n_groups, n_inst, b->ipg));
+    if (b->n_sends >= (1ull << 32))
+        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends per call");
+    if (b->n_sends && !b->n_groups) return fail(e, MPX_E_INVAL, "sends without a window");
+    const bool min = e->cfg.mode == MPX_MODE_MIN;
+    const int32_t N = e->cfg.n_replicas;
+    const bool thrifty = (b->flags & MPX_AB_THRIFTY) != 0;
+    if (min && b->n_sends && (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
+        return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
+    // the device kernels trust the offsets and the ranges
+    std::vector<uint32_t> nils;  // nils[i] = nil records among window records [0, i)
+    if (min && b->n_sends) {
+        nils.assign(n_inst + 1, 0);
+        for (size_t i = 0; i < n_inst; ++i) {
+            if (b->log_cmd_off[i] > b->log_cmd_off[i + 1] || b->log_cmd_off[i + 1] > b->n_log_cmds)
+                return fail(e, MPX_E_INVAL, "log_cmd_off must be non-decreasing and <= n_log_cmds");
+            nils[i + 1] = nils[i] + (b->log_recs[i].status == MPX_STATUS_NIL ? 1u : 0u);
+        }
+        if (b->n_log_cmds && (!b->log_op || !b->log_key || !b->log_val))
+            return fail(e, MPX_E_INVAL, "null log command arrays");
+    }
+    bool nil_hit = false;
+    for (size_t s = 0; s < b->n_sends; ++s) {
+        const mpx_accept_send& x = b->sends[s];
+        if (!(x.flags & MPX_PH_ACCEPT)) continue;
+        const int64_t idx = (int64_t)x.instance - b->inst_base;
+        if (idx < 0 || (uint64_t)idx >= n_inst)
+            return fail(e, MPX_E_INVAL, "a send names an instance outside the window");
+        if (x.first_cmd > b->n_cmds || x.n_cmds > b->n_cmds - x.first_cmd ||
+            (x.n_cmds && (!b->cmd_op || !b->cmd_key || !b->cmd_val)))
+            return fail(e, MPX_E_INVAL, "a send's commands are outside the command arrays");
+        const size_t g = (size_t)idx / b->ipg;
+        const int32_t self = b->groups[g].self_id;
+        if (self < 0 || self >= N) return fail(e, MPX_E_INVAL, "self_id outside [0, N)");
+        if (!min) continue;
+        const int64_t first = (int64_t)(g * b->ipg), lc = (int64_t)x.last_committed - b->inst_base;
+        if (lc >= idx || lc < first - 1)
+            return fail(e, MPX_E_INVAL, "last_committed must lie in [first_g - 1, instance)");
+        const uint32_t dests = accept_dests(e->cfg.mode, N, self, thrifty, b->alive_mask);
+        for (int32_t q = 0; q < N; ++q) {
+            if (!((dests >> q) & 1u)) continue;
+            const int64_t pc = (int64_t)b->peer_commits[g * N + q] - b->inst_base;
+            const int64_t lo = pc < first ? first : pc + 1;
+            if (lo <= lc && nils[lc + 1] != nils[lo]) nil_hit = true;
+        }
+    }
+    if (nil_hit)
+        return fail(e, MPX_E_NIL_INSTANCE, "a nil instance inside a catch-up range");
+    if (!mpx::launch_encode_accepts || !mpx::accepts_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
+    CK(begin(e));
+    if (b->n_sends)
+        GROW(e, e->ab_work, mpx::accepts_work_bytes((uint32_t)N, b->n_sends, n_inst));
+    Stage L(e);
+    const size_t m = b->n_cmds, lm = min ? b->n_log_cmds : 0, li = min && b->n_sends ? n_inst : 0;
+    const Slot s_snd = L.add(b->n_sends * sizeof(mpx_accept_send)),
+               s_grp = L.add(b->n_sends ? b->n_groups * sizeof(mpx_proposer_group) : 0),
+               s_pc = L.add(min && b->n_sends ? b->n_groups * (size_t)N * 4 : 0),
+               s_op = L.add(b->cmd_op ? m : 0), s_key = L.add(b->cmd_key ? m * 8 : 0),
+               s_val = L.add(b->cmd_val ? m * 8 : 0), s_lrec = L.add(li * sizeof(mpx_log_rec)),
+               s_lcoff = L.add(li ? (li + 1) * 8 : 0), s_lop = L.add(b->log_op ? lm : 0),
+               s_lkey = L.add(b->log_key ? lm * 8 : 0), s_lval = L.add(b->log_val ? lm * 8 : 0),
+               s_out = L.add(out_cap), s_off = L.add(((size_t)N + 1) * 8);
+    CK(L.commit());
+    CK(L.in(s_snd, b->sends));
+    CK(L.in(s_grp, b->groups));
+    CK(L.in(s_pc, b->peer_commits));
+    CK(L.in(s_op, b->cmd_op));
+    CK(L.in(s_key, b->cmd_key));
+    CK(L.in(s_val, b->cmd_val));
+    CK(L.in(s_lrec, b->log_recs));
+    CK(L.in(s_lcoff, b->log_cmd_off));
+    CK(L.in(s_lop, b->log_op));
+    CK(L.in(s_lkey, b->log_key));
+    CK(L.in(s_lval, b->log_val));
+    mpx_accept_batch d = *b;
+    d.sends = L.at<mpx_accept_send>(s_snd);
+    d.groups = L.at<mpx_proposer_group>(s_grp);
+    d.peer_commits = L.at<int32_t>(s_pc);
+    d.cmd_op = L.at<uint8_t>(s_op);
+    d.cmd_key = L.at<int64_t>(s_key);
+    d.cmd_val = L.at<int64_t>(s_val);
+    d.log_recs = L.at<mpx_log_rec>(s_lrec);
+    d.log_cmd_off = L.at<uint64_t>(s_lcoff);
+    d.log_op = L.at<uint8_t>(s_lop);
+    d.log_key = L.at<int64_t>(s_lkey);
+    d.log_val = L.at<int64_t>(s_lval);
+    CK(mpx_encode_accepts_dev(e, &d, L.at<uint8_t>(s_out), out_cap, L.at<uint64_t>(s_off),
+                              e->stream));
+    CK(L.out(s_off, dest_off));
+    CK(finish(e));
+    if (dest_off[N] > out_cap) return fail(e, MPX_E_INVAL, "out_cap is smaller than the frames");
+    CK(L.out(s_out, out, dest_off[N]));
+    return finish(e);
 }
 
 // ---- §8(f) ranks 3/4: instance-log encoding -------------------------------------------------

@@ -200,6 +200,22 @@ hipError_t launch_encode_accept_replies(
     uint32_t n_dest, uint8_t* out, uint64_t* dest_off, void* work, uint64_t work_bytes,
     uint32_t* err, hipStream_t stream);
 
+// ---- the proposer side (mpx_propose_handle, mpx_encode_accepts; proposer.hip) ---------------
+// Weak: a build of engine.cpp without proposer.hip links, and the entry points then return
+// MPX_E_UNSUPPORTED.
+// One launch: no scratch, no control words.
+__attribute__((weak)) hipError_t launch_propose_handle(
+    int mode, mpx_proposer_group* groups, uint64_t n_groups, const uint64_t* prop_off,
+    const uint64_t* send_off, mpx_acceptor_state* st, mpx_inst_state* lb, uint64_t n_inst,
+    int32_t base, uint32_t ipg, int32_t nrep, mpx_accept_send* sends, uint32_t* err,
+    hipStream_t stream);
+__attribute__((weak)) uint64_t accepts_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst,
+                                                  Carver&& c = Carver());
+// b: a host struct of device pointers; nothing is written at or past out + out_cap
+__attribute__((weak)) hipError_t launch_encode_accepts(
+    int mode, int32_t nrep, const mpx_accept_batch* b, uint8_t* out, uint64_t out_cap,
+    uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

@@ -12,6 +12,8 @@ Names and argument meaning follow the reference handlers they replace:
   encode_replies      <- the ProposeReplyTS fan-out (ReplyProposeTS per executed command)
   accept_handle       <- bareminpaxos / paxos  handleAccept (the acceptor's half of Phase 2)
   encode_accept_replies <- replyAccept -> SendMsg: the AcceptReply frames per leader connection
+  propose_handle      <- bareminpaxos / paxos  handlePropose (which proposals become an instance)
+  encode_accepts      <- bcastAccept -> SendMsg: the Accept frames per peer connection
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -446,6 +448,92 @@ class Engine:
         self._check(self.lib.mpx_encode_accept_replies_dev(self.h, d_replies, d_reply_to, n,
                                                            n_dest, d_out, d_off, stream),
                     "mpx_encode_accept_replies_dev")
+
+    # ---- the proposer side: handlePropose and the Accept bytes --------------------------------
+    def propose_handle(self, groups, prop_off, st, inst_base=0, ipg=None, lb=None):
+        """groups: PROPOSER_GROUP (copied; crt_instance comes back advanced); prop_off u64[G+1]:
+        group g's drained proposals; st: ACCEPTOR_STATE of the window (copied); lb: optional
+        INST_STATE of the window (copied). Returns (groups, st, lb, sends ACCEPT_SEND, send_off
+        u64[G+1])."""
+        groups = np.array(np.atleast_1d(groups), dtype=R.PROPOSER_GROUP, copy=True)
+        prop_off = _c(prop_off, np.uint64)
+        st = np.array(st, dtype=R.ACCEPTOR_STATE, copy=True)
+        lb = None if lb is None else np.array(lb, dtype=R.INST_STATE, copy=True)
+        G = len(groups)
+        ipg = (len(st) // G if G else 0) if ipg is None else ipg
+        n = [int(prop_off[g + 1]) - int(prop_off[g]) for g in range(G)]
+        cap = sum(-(-x // R.PROPOSE_MAX_BATCH) for x in n if x > 0)
+        sends = np.zeros(max(cap, 1), R.ACCEPT_SEND)
+        send_off = np.zeros(G + 1, np.uint64)
+        rc = self.lib.mpx_propose_handle(self.h, _ptr(groups), G, _ptr(prop_off), _ptr(st),
+                                         _ptr(lb), len(st), inst_base, ipg, _ptr(send_off),
+                                         _ptr(sends), cap)
+        self._check(rc, "mpx_propose_handle")
+        return groups, st, lb, sends[:cap], send_off
+
+    def propose_handle_dev(self, d_groups, n_groups, d_prop_off, d_send_off, d_st, d_lb, n_inst,
+                           inst_base, ipg, d_sends, stream=None):
+        rc = self.lib.mpx_propose_handle_dev(self.h, d_groups, n_groups, d_prop_off, d_send_off,
+                                             d_st, d_lb, n_inst, inst_base, ipg, d_sends, stream)
+        self._check(rc, "mpx_propose_handle_dev")
+
+    def encode_accepts(self, sends, groups, cmds, inst_base=0, ipg=None, peer_commits=None,
+                       log=None, thrifty=False, alive_mask=0xFFFF, out_cap=None):
+        """sends: ACCEPT_SEND; groups: PROPOSER_GROUP; cmds: (op, key, val) the new commands;
+        peer_commits: int32[G, N] (MIN); log: (recs LOG_REC[n_inst], cmd_off u64[n_inst+1], op,
+        key, val) the window's log (MIN). Returns (bytes uint8, dest_off u64[N+1]): peer q's
+        connection receives out[dest_off[q]:dest_off[q+1]]."""
+        sends = _c(sends, R.ACCEPT_SEND)
+        groups = _c(np.atleast_1d(groups), R.PROPOSER_GROUP)
+        op, key, val = _c(cmds[0], np.uint8), _c(cmds[1], np.int64), _c(cmds[2], np.int64)
+        G, N = len(groups), self.n_replicas
+        keep = [sends, groups, op, key, val]
+        b = _lib.MpxAcceptBatch()
+        b.sends, b.n_sends, b.inst_base = _ptr(sends), len(sends), inst_base
+        b.groups, b.n_groups = _ptr(groups), G
+        b.cmd_op, b.cmd_key, b.cmd_val, b.n_cmds = _ptr(op), _ptr(key), _ptr(val), len(op)
+        b.flags = R.AB_THRIFTY if thrifty else 0
+        b.alive_mask = alive_mask
+        n_inst = 0
+        if log is not None:
+            lrec, lcoff = _c(log[0], R.LOG_REC), _c(log[1], np.uint64)
+            lop, lkey, lval = _c(log[2], np.uint8), _c(log[3], np.int64), _c(log[4], np.int64)
+            keep += [lrec, lcoff, lop, lkey, lval]
+            n_inst = len(lrec)
+            b.log_recs, b.log_cmd_off = _ptr(lrec), _ptr(lcoff)
+            b.log_op, b.log_key, b.log_val, b.n_log_cmds = _ptr(lop), _ptr(lkey), _ptr(lval), len(lop)
+        if peer_commits is not None:
+            pc = _c(peer_commits, np.int32)
+            keep.append(pc)
+            b.peer_commits = _ptr(pc)
+        if ipg is None and log is None:
+            raise ValueError("encode_accepts: ipg is needed when no log gives the window's size")
+        b.ipg = (n_inst // G if G else 0) if ipg is None else ipg
+        if out_cap is None:  # every frame with its largest possible catch-up log
+            sel = sends[(sends["flags"] & R.PH_ACCEPT) != 0]
+            logb = 0
+            if log is not None and n_inst:
+                k = np.diff(lcoff.astype(np.int64))
+                per = 18 * b.ipg + 17 * int(k.reshape(G, -1).sum(axis=1).max()) if G else 0
+                logb = per
+            out_cap = int((28 * len(sel) + 17 * int(sel["n_cmds"].sum()) + logb * len(sel)) * N)
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        off = np.zeros(N + 1, np.uint64)
+        rc = self.lib.mpx_encode_accepts(self.h, C.byref(b), _ptr(out), out_cap, _ptr(off))
+        self._check(rc, "mpx_encode_accepts")
+        del keep
+        return out[:int(off[-1])], off
+
+    def encode_accepts_reserve(self, max_sends, max_n_inst, max_log_cmds=0):
+        self._check(self.lib.mpx_encode_accepts_reserve(self.h, max_sends, max_n_inst,
+                                                        max_log_cmds),
+                    "mpx_encode_accepts_reserve")
+
+    def encode_accepts_dev(self, batch, d_out, out_cap, d_dest_off, stream=None):
+        """batch: _lib.MpxAcceptBatch of device pointers"""
+        self._check(self.lib.mpx_encode_accepts_dev(self.h, C.byref(batch), d_out, out_cap,
+                                                    d_dest_off, stream),
+                    "mpx_encode_accepts_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

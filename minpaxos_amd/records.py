@@ -103,6 +103,43 @@ AH_REPLIED, AH_STORED, AH_REQUEUE = 1, 2, 4
 # frame bytes of one AcceptReply on a peer connection (code byte + Marshal), by mode
 ACCEPT_REPLY_FRAME = {MODE_MIN: 14, MODE_CLASSIC: 10}
 
+# the proposer side (mpx_propose_handle / mpx_encode_accepts)
+# mpx_proposer_group  <- r.defaultBallot, r.Id, r.Leader, prepareOKs, r.crtInstance, r.committedUpTo
+PROPOSER_GROUP = np.dtype([("default_ballot", "<i4"), ("self_id", "<i4"), ("leader", "<i4"),
+                           ("prepare_oks", "<i4"), ("crt_instance", "<i4"),
+                           ("committed_upto", "<i4"), ("pad", "<u4", (2,))])
+# mpx_accept_send  <- one run of handlePropose: a batch of proposals and what became of it
+ACCEPT_SEND = np.dtype([("instance", "<i4"), ("ballot", "<i4"), ("last_committed", "<i4"),
+                        ("flags", "<u4"), ("first_cmd", "<u8"), ("n_cmds", "<u4"), ("pad", "<u4")])
+PROPOSE_MAX_BATCH = 5000
+PH_ACCEPT, PH_NOT_LEADER, PH_REFUSED, PH_PREPARE = 1, 2, 4, 8
+AB_THRIFTY = 1
+
+
+def varint_len(x):
+    """bytes of binary.PutVarint(x), x >= 0"""
+    u, n = x << 1, 1
+    while u >= 0x80:
+        u >>= 7
+        n += 1
+    return n
+
+
+def log_instance_bytes(n_cmds):
+    """Instance.Marshal: Ballot, Status, V(k), k Commands"""
+    return 8 + varint_len(n_cmds) + 17 * n_cmds
+
+
+def accept_frame_bytes(mode, n_cmds, log_cmd_counts=()):
+    """one Accept on a peer connection (code byte + Marshal); MIN: log_cmd_counts = len(Cmds) of
+    every CatchUpLog instance"""
+    if mode == MODE_MIN:
+        return (17 + varint_len(n_cmds) + 17 * n_cmds + varint_len(len(log_cmd_counts)) +
+                sum(log_instance_bytes(k) for k in log_cmd_counts))
+    return 13 + varint_len(n_cmds) + 17 * n_cmds
+
+
+assert PROPOSER_GROUP.itemsize == 32 and ACCEPT_SEND.itemsize == 32
 assert ACCEPT_MSG.itemsize == 16 and ACCEPTOR_STATE.itemsize == 16
 assert ACCEPTOR_GROUP.itemsize == 8
 assert LOG_REC.itemsize == 16
