@@ -37,6 +37,12 @@
  *                            paxos.(*Replica).handlePropose  src/paxos/paxos.go:388-443: which
  *                            drained proposals become an instance, and mpx_encode_accepts the
  *                            Accept frames bcastAccept (:450-520 / :299-331) writes to every peer
+ *   mpx_unmarshal_frames  <- Accept / Commit / PrepareReply.Unmarshal with Instance.Unmarshal and
+ *                            Command.Unmarshal (minpaxosprotomarsh.go:470-507, :648-672, :352-387,
+ *                            :126-153 / paxosprotomarsh.go:244-268, :403-430, :152-176;
+ *                            statemarsh.go:21-39): the frames mpx_decode_stream found, as the
+ *                            records mpx_accept_handle takes and the SoA commands and catch-up log
+ *                            mpx_apply, mpx_encode_log and mpx_accept_batch.log_* take
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -69,12 +75,14 @@
  *   - the tally (mpx_accept_tally_dev), CLASSIC prepare (mpx_prepare_select_dev), apply
  *     (mpx_apply_dev), group-step and durable-log replay (mpx_replay_durable_dev) kernels keep
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
- *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup:
+ *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
+ *     and the encoders and mpx_unmarshal_frames_dev keep their offsets and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
- *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve, or a host-
- *     pointer mpx_apply / mpx_replay_durable call that needs more) frees the old buffers and
+ *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
+ *     mpx_unmarshal_frames_reserve, or a host-pointer mpx_apply / mpx_replay_durable /
+ *     mpx_unmarshal_frames call that needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
  *     returns MPX_E_NIL_INSTANCE / MPX_E_BAD_ID and the outputs are unspecified.
@@ -93,7 +101,8 @@ extern "C" {
                               6: + mpx_replay_durable_reserve; 7: + mpx_group_step_events;
                               8: + MPX_FLAG_STEP_ONE_LAUNCH; additive since, same number:
                               mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev],
-                              mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev] */
+                              mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev],
+                              mpx_unmarshal_frames[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -544,7 +553,7 @@ int mpx_decode_peer_stream_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len
  *   PrepareReply -> mpx_prepare_reply_min (MIN) / mpx_prepare_reply (CLASSIC) with value_id =
  *                   the index of the frame's mpx_var_frame (its Command slice), AND an
  *                   mpx_var_frame
- *   Accept / Commit -> mpx_var_frame (the host unmarshals them from the byte ranges)
+ *   Accept / Commit -> mpx_var_frame (mpx_unmarshal_frames turns the byte ranges into records)
  *   other fixed-size frames -> mpx_peer_frame                                               */
 typedef struct mpx_var_frame {
     uint32_t offset;      /* the frame's code byte                                          */
@@ -887,6 +896,88 @@ int mpx_encode_accepts_reserve(mpx_engine* eng, size_t max_sends, size_t max_n_i
  * cmd_op, log_op and d_out any address.                                                         */
 int mpx_encode_accepts_dev(mpx_engine* eng, const mpx_accept_batch* b, uint8_t* d_out,
                            size_t out_cap, uint64_t* d_dest_off, void* stream);
+
+/* ---- Accept / Commit / PrepareReply payloads: Unmarshal in a batch ---------------------------
+ * The inverse of mpx_encode_accepts: from the mpx_var_frame ranges mpx_decode_stream[_dev] left
+ * (the same buf, the same offsets) to the records and arrays the rest of the engine takes, by
+ * mpx_config.mode:
+ *                           MIN (minpaxosprotomarsh.go)   CLASSIC (paxosprotomarsh.go)
+ *   Accept.Unmarshal        :470-507                      :244-268
+ *   Commit.Unmarshal        :648-672                      :403-430
+ *   PrepareReply.Unmarshal  :352-387                      :152-176
+ *   Instance.Unmarshal      :126-153                      -
+ *   Command.Unmarshal       statemarsh.go:21-39 (Op u8, K i64, V i64)
+ * Header fields sit at offset + 1, little endian: MIN Accept LeaderId, Instance, Ballot,
+ * LastCommitted; CLASSIC Accept and every Commit LeaderId, Instance, Ballot. A PrepareReply's fixed
+ * fields are already in mpx_decode_stream's prepare records (their value_id is the frame's var
+ * index); only its Command slice and, in MIN, its CatchUpLog are unmarshalled here (its
+ * LastCommitted is the i32 at offset + 14).
+ * Everything is in stream order, that is, var order:
+ *   accepts / commits   one slot per frame of that code (compacted), value_id = the frame's index
+ *                       in var; accept_last_committed slot-aligned with accepts
+ *   cmd_off             n_var+1 entries, one per var frame of any code: the exclusive prefix sums of
+ *                       var[i].n_cmds; frame i's Command slice is commands [cmd_off[i], cmd_off[i+1])
+ *                       of op / key / val
+ *   log_inst_off        n_var+1 entries, the prefix sums of var[i].n_log: frame i's CatchUpLog is
+ *                       log records [log_inst_off[i], log_inst_off[i+1]). Commit frames and every
+ *                       CLASSIC frame have n_log = 0
+ *   log_recs, log_cmd_off, log_op / log_key / log_val
+ *                       the log instances and their commands, log_cmd_off the prefix sums of the
+ *                       instances' command counts: the layout mpx_encode_log and
+ *                       mpx_accept_batch.log_* take, so the output of one is a legal input of the
+ *                       other
+ * inst_no of a log record is the sender's numbering: both senders build ranges that end at the
+ * frame's LastCommitted (bcastAccept bareminpaxos.go:496-506, handlePrepare :743), so record j of a
+ * frame with m log instances is instance LastCommitted - m + 1 + j. The receivers index the log by
+ * position, j = record - log_inst_off[i] (bareminpaxos.go:937 and the commented-out :778).
+ * The counts in *res are always complete; an element at or past its capacity is not written (as in
+ * mpx_decode_stream), and a capacity of 0 may come with null pointers. With d_n_var the entries of
+ * cmd_off / log_inst_off past the processed frames repeat the totals.                          */
+typedef struct mpx_unmarshal_out {
+    mpx_accept_msg* accepts;         /* code 9 frames, stream order; value_id = the frame's var index */
+    int32_t* accept_last_committed;  /* slot-aligned with accepts (MIN; CLASSIC writes -1)            */
+    size_t accept_cap;
+    mpx_accept_msg* commits;         /* code 10 frames, same record (leader_id, instance, ballot)     */
+    size_t commit_cap;
+    uint64_t* cmd_off;               /* n_var+1: frame i's Command slice = [cmd_off[i], cmd_off[i+1]) */
+    uint8_t* op; int64_t* key; int64_t* val; size_t cmd_cap;
+    uint64_t* log_inst_off;          /* n_var+1: frame i's CatchUpLog = log records [..[i], ..[i+1])  */
+    mpx_log_rec* log_recs;           /* ballot, status, inst_no, pad = 0                              */
+    uint64_t* log_cmd_off;           /* log_inst_cap+1                                                */
+    size_t log_inst_cap;
+    uint8_t* log_op; int64_t* log_key; int64_t* log_val; size_t log_cmd_cap;
+} mpx_unmarshal_out;
+
+typedef struct mpx_unmarshal_result {
+    uint64_t n_accepts, n_commits, n_cmds, n_log_inst, n_log_cmds;  /* always complete */
+    uint64_t n_var;                                                 /* frames processed */
+} mpx_unmarshal_result; /* 48 B */
+
+/* host pointers, synchronous; stages like the other host forms. The frames are validated before
+ * anything is launched; MPX_E_INVAL for a frame outside [0, len), cmds_off + 17 * n_cmds or log_off
+ * outside the frame (or a header that does not fit before cmds_off, or n_log != 0 on a frame
+ * without a log), a code other than 9, 10 or 12, and frames that overlap or are not ascending by
+ * offset. A CatchUpLog whose walk does not end exactly at the frame's end: MPX_E_INVAL.          */
+int mpx_unmarshal_frames(mpx_engine* eng, const uint8_t* buf, size_t len, const mpx_var_frame* var,
+                         size_t n_var, const mpx_unmarshal_out* out, mpx_unmarshal_result* res);
+/* scratch for _dev calls of up to max_var frames that carry up to max_log_inst catch-up instances
+ * in total (grows only). The scratch lives in the handle: like the other *_dev calls that keep
+ * scratch there, unmarshals of one handle run in one stream order, and a larger reserve
+ * invalidates graphs captured before it.                                                        */
+int mpx_unmarshal_frames_reserve(mpx_engine* eng, size_t max_var, size_t max_log_inst);
+/* device form: `out` is a host struct of device pointers. The frames are trusted (they come from
+ * mpx_decode_stream_dev). d_n_var (optional, device): min(*d_n_var, n_var) frames are processed, so
+ * the call can be captured right behind mpx_decode_stream_dev with n_var = var_cap and
+ * d_n_var = &d_stream_res->n_var. A catch-up walk that does not end exactly at its frame's end, or
+ * more catch-up instances than the reserve was told, is reported through the handle's error word
+ * (MPX_E_INVAL at the next synchronising call); that frame's log records are unspecified. Never
+ * allocates or synchronises; needs mpx_unmarshal_frames_reserve first. d_buf may be read up to len
+ * rounded up to 16, never at or past it. Alignment: d_buf 16 bytes, as for the decoders (any other
+ * address is rejected with MPX_E_INVAL); d_var, accepts, commits, log_recs 16; offsets, keys,
+ * values, d_n_var, d_res 8; accept_last_committed 4; op and log_op any address.                  */
+int mpx_unmarshal_frames_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
+                             const mpx_var_frame* d_var, size_t n_var, const uint64_t* d_n_var,
+                             const mpx_unmarshal_out* out, mpx_unmarshal_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

@@ -45,6 +45,14 @@ class MpxAcceptBatch(C.Structure):
                 ("n_log_cmds", _sz), ("flags", C.c_uint32), ("alive_mask", C.c_uint32)]
 
 
+class MpxUnmarshalOut(C.Structure):
+    _fields_ = [("accepts", _p), ("accept_last_committed", _p), ("accept_cap", _sz),
+                ("commits", _p), ("commit_cap", _sz), ("cmd_off", _p), ("op", _p), ("key", _p),
+                ("val", _p), ("cmd_cap", _sz), ("log_inst_off", _p), ("log_recs", _p),
+                ("log_cmd_off", _p), ("log_inst_cap", _sz), ("log_op", _p), ("log_key", _p),
+                ("log_val", _p), ("log_cmd_cap", _sz)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -102,6 +110,10 @@ SIGNATURES = {
     "mpx_encode_accepts": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p]),
     "mpx_encode_accepts_reserve": (C.c_int, [_p, _sz, _sz, _sz]),
     "mpx_encode_accepts_dev": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p, _p]),
+    "mpx_unmarshal_frames": (C.c_int, [_p, _p, _sz, _p, _sz, C.POINTER(MpxUnmarshalOut), _p]),
+    "mpx_unmarshal_frames_reserve": (C.c_int, [_p, _sz, _sz]),
+    "mpx_unmarshal_frames_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, C.POINTER(MpxUnmarshalOut),
+                                           _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

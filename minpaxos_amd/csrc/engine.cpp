@@ -72,7 +72,9 @@ struct mpx_engine {
     mpx::KvTable kv{};
     bool kv_ready = false;
     // the families' scratch: grown by the host forms and the *_reserve calls, never by a _dev form
-    DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work, ab_work;
+    DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work, ab_work,
+        um_work;
+    size_t um_var_cap = 0, um_log_cap = 0;  // what um_work was last sized for (mpx_unmarshal_frames)
     mpx::ApplyOpts apply{};  // mpx_config.apply_* (fixed for the handle's life)
     // replica-sized mpx_apply calls: pinned, GPU-mapped staging the one-launch kernel reads the
     // commands from and writes the results to (no DMA copies on the call's path)
@@ -389,7 +391,8 @@ int mpx_close(mpx_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->comm) ncclCommDestroy(e->comm);
     for (DevBuf* x : {&e->arena, &e->apply_work, &e->decode_work, &e->stream_work, &e->fan_work,
-                      &e->log_work, &e->replay_work, &e->are_work, &e->ab_work, &e->worklist})
+                      &e->log_work, &e->replay_work, &e->are_work, &e->ab_work, &e->um_work,
+                      &e->worklist})
         if (x->p) (void)hipFree(x->p);
     if (e->pin_io.p) (void)hipHostFree(e->pin_io.p);
     if (e->pin_staged.p) (void)hipHostFree(e->pin_staged.p);
@@ -1552,6 +1555,165 @@ int mpx_encode_accepts(mpx_engine* e, const mpx_accept_batch* b, uint8_t* out, s
     if (dest_off[N] > out_cap) return fail(e, MPX_E_INVAL, "out_cap is smaller than the frames");
     CK(L.out(s_out, out, dest_off[N]));
     return finish(e);
+}
+
+// ---- Accept / Commit / PrepareReply payloads: Unmarshal in a batch ---------------------------
+// (weak launchers, like the proposer's)
+namespace {
+const char* const kNoUnmarshal = "mpx_unmarshal_frames: the unmarshal kernels are not built in";
+
+int unmarshal_args(mpx_engine* e, const void* buf, size_t len, const void* var, size_t n_var,
+                   const mpx_unmarshal_out* o, const void* res) {
+    if (!o || !res || (len && !buf) || (n_var && (!var || !len)))
+        return fail(e, MPX_E_INVAL, "null argument");
+    if ((o->accept_cap && (!o->accepts || !o->accept_last_committed)) ||
+        (o->commit_cap && !o->commits) || (o->cmd_cap && (!o->op || !o->key || !o->val)) ||
+        (o->log_inst_cap && !o->log_recs) ||
+        (o->log_cmd_cap && (!o->log_op || !o->log_key || !o->log_val)))
+        return fail(e, MPX_E_INVAL, "a capacity above 0 needs its arrays");
+    CK(decode_limit(e, len));
+    return record_limit(e, n_var);
+}
+// catch-up instances the scratch of a call on len bytes is carved for (an Instance is 9 bytes at
+// least); launch_unmarshal takes the same minimum
+uint64_t unmarshal_log_slots(const mpx_engine* e, size_t n_var, size_t len) {
+    if (e->cfg.mode != MPX_MODE_MIN || !n_var) return 0;
+    return std::min<uint64_t>(len / 9, e->um_log_cap);
+}
+// bytes from the code byte to V(len(Command))
+uint32_t var_header(int mode, uint32_t code) {
+    if (mode == MPX_MODE_MIN)
+        return code == MPX_PEER_ACCEPT ? 17 : code == MPX_PEER_COMMIT ? 13 : 18;
+    return code == MPX_PEER_PREPARE_REPLY ? 10 : 13;
+}
+}  // namespace
+
+int mpx_unmarshal_frames_reserve(mpx_engine* e, size_t max_var, size_t max_log_inst) {
+    if (!e) return MPX_E_INVAL;
+    CK(record_limit(e, max_var));
+    CK(record_limit(e, max_log_inst));
+    if (!mpx::unmarshal_work_bytes) return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
+    e->um_var_cap = std::max(e->um_var_cap, max_var);
+    e->um_log_cap = std::max(e->um_log_cap, max_log_inst);
+    return reserve(e, e->um_work, mpx::unmarshal_work_bytes(e->um_var_cap, e->um_log_cap));
+}
+
+int mpx_unmarshal_frames_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
+                             const mpx_var_frame* d_var, size_t n_var, const uint64_t* d_n_var,
+                             const mpx_unmarshal_out* out, mpx_unmarshal_result* d_res,
+                             void* stream) {
+    if (!e) return MPX_E_INVAL;
+    CK(unmarshal_args(e, d_buf, len, d_var, n_var, out, d_res));
+    if ((uintptr_t)d_buf & 15)
+        return fail(e, MPX_E_INVAL, "mpx_unmarshal_frames_dev: d_buf must be 16-byte aligned");
+    if (!mpx::launch_unmarshal || !mpx::unmarshal_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
+    CK(reserved(e, e->um_work,
+                mpx::unmarshal_work_bytes(n_var, unmarshal_log_slots(e, n_var, len)),
+                "mpx_unmarshal_frames_dev", "mpx_unmarshal_frames_reserve(n_var, n_log_inst)"));
+    HIPCHK(e, mpx::launch_unmarshal(e->cfg.mode, d_buf, len, d_var, n_var, d_n_var, out, d_res,
+                                    e->um_log_cap, e->um_work.p, e->um_work.cap, e->d_err,
+                                    pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_unmarshal_frames(mpx_engine* e, const uint8_t* buf, size_t len, const mpx_var_frame* var,
+                         size_t n_var, const mpx_unmarshal_out* out, mpx_unmarshal_result* res) {
+    if (!e) return MPX_E_INVAL;
+    CK(unmarshal_args(e, buf, len, var, n_var, out, res));
+    // the device kernels trust the frames
+    const bool min = e->cfg.mode == MPX_MODE_MIN;
+    uint64_t prev_end = 0, n_acc = 0, n_com = 0, n_cmds = 0, n_log = 0;
+    for (size_t i = 0; i < n_var; ++i) {
+        const mpx_var_frame& f = var[i];
+        if (f.code != MPX_PEER_ACCEPT && f.code != MPX_PEER_COMMIT &&
+            f.code != MPX_PEER_PREPARE_REPLY)
+            return fail(e, MPX_E_INVAL, "a frame's code is not Accept, Commit or PrepareReply");
+        const uint64_t end = (uint64_t)f.offset + f.length;
+        if (!f.length || f.offset >= len || end > len)
+            return fail(e, MPX_E_INVAL, "a frame lies outside [0, len)");
+        if (f.offset < prev_end)
+            return fail(e, MPX_E_INVAL, "frames overlap or are not ascending by offset");
+        prev_end = end;
+        const uint64_t cmds_end = (uint64_t)f.cmds_off + 17ull * f.n_cmds;
+        if (f.cmds_off < (uint64_t)f.offset + var_header(e->cfg.mode, f.code) || cmds_end > end)
+            return fail(e, MPX_E_INVAL, "a frame's Command slice lies outside the frame");
+        if (f.log_off < cmds_end || f.log_off > end)
+            return fail(e, MPX_E_INVAL, "a frame's log_off lies outside the frame");
+        const bool has_log = min && f.code != MPX_PEER_COMMIT;
+        if (has_log ? f.n_log > (end - f.log_off) / 9 : f.n_log != 0)
+            return fail(e, MPX_E_INVAL, "a frame's n_log does not fit the frame");
+        n_acc += f.code == MPX_PEER_ACCEPT;
+        n_com += f.code == MPX_PEER_COMMIT;
+        n_cmds += f.n_cmds;
+        n_log += f.n_log;
+    }
+    if (!mpx::launch_unmarshal || !mpx::unmarshal_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
+    CK(begin(e));
+    e->um_log_cap = std::max<size_t>(e->um_log_cap, n_log);
+    GROW(e, e->um_work, mpx::unmarshal_work_bytes(n_var, unmarshal_log_slots(e, n_var, len)));
+    const size_t na = std::min<uint64_t>(out->accept_cap, n_acc),
+                 nc = std::min<uint64_t>(out->commit_cap, n_com),
+                 m = std::min<uint64_t>(out->cmd_cap, n_cmds),
+                 li = std::min<uint64_t>(out->log_inst_cap, n_log),
+                 lm = n_log ? std::min<uint64_t>(out->log_cmd_cap, len / 17) : 0;
+    Stage L(e);
+    const Slot s_buf = L.add(len), s_var = L.add(n_var * sizeof(mpx_var_frame)),
+               s_acc = L.add(na * sizeof(mpx_accept_msg)), s_alc = L.add(na * 4),
+               s_com = L.add(nc * sizeof(mpx_accept_msg)),
+               s_coff = L.add(out->cmd_off ? (n_var + 1) * 8 : 0), s_op = L.add(m),
+               s_key = L.add(m * 8), s_val = L.add(m * 8),
+               s_loff = L.add(out->log_inst_off ? (n_var + 1) * 8 : 0),
+               s_lrec = L.add(li * sizeof(mpx_log_rec)),
+               s_lcoff = L.add(out->log_cmd_off ? (li + 1) * 8 : 0), s_lop = L.add(lm),
+               s_lkey = L.add(lm * 8), s_lval = L.add(lm * 8),
+               s_res = L.add(sizeof(mpx_unmarshal_result));
+    CK(L.commit());
+    CK(L.in(s_buf, buf));
+    CK(L.in(s_var, var));
+    mpx_unmarshal_out d{};
+    d.accepts = L.at<mpx_accept_msg>(s_acc);
+    d.accept_last_committed = L.at<int32_t>(s_alc);
+    d.accept_cap = na;
+    d.commits = L.at<mpx_accept_msg>(s_com);
+    d.commit_cap = nc;
+    d.cmd_off = L.at<uint64_t>(s_coff, out->cmd_off);
+    d.op = L.at<uint8_t>(s_op);
+    d.key = L.at<int64_t>(s_key);
+    d.val = L.at<int64_t>(s_val);
+    d.cmd_cap = m;
+    d.log_inst_off = L.at<uint64_t>(s_loff, out->log_inst_off);
+    d.log_recs = L.at<mpx_log_rec>(s_lrec);
+    d.log_cmd_off = L.at<uint64_t>(s_lcoff, out->log_cmd_off);
+    d.log_inst_cap = li;
+    d.log_op = L.at<uint8_t>(s_lop);
+    d.log_key = L.at<int64_t>(s_lkey);
+    d.log_val = L.at<int64_t>(s_lval);
+    d.log_cmd_cap = lm;
+    CK(mpx_unmarshal_frames_dev(e, L.at<uint8_t>(s_buf), len, L.at<mpx_var_frame>(s_var), n_var,
+                                nullptr, &d, L.at<mpx_unmarshal_result>(s_res), e->stream));
+    CK(L.out(s_res, res));
+    const int rc = finish(e);
+    if (rc == MPX_E_INVAL)
+        return fail(e, MPX_E_INVAL, "a CatchUpLog does not end at its frame's end");
+    if (rc) return rc;
+    const size_t lc = std::min<uint64_t>(res->n_log_cmds, lm);
+    CK(L.out(s_acc, out->accepts, na * sizeof(mpx_accept_msg)));
+    CK(L.out(s_alc, out->accept_last_committed, na * 4));
+    CK(L.out(s_com, out->commits, nc * sizeof(mpx_accept_msg)));
+    if (out->cmd_off) CK(L.out(s_coff, out->cmd_off));
+    CK(L.out(s_op, out->op, m));
+    CK(L.out(s_key, out->key, m * 8));
+    CK(L.out(s_val, out->val, m * 8));
+    if (out->log_inst_off) CK(L.out(s_loff, out->log_inst_off));
+    CK(L.out(s_lrec, out->log_recs, li * sizeof(mpx_log_rec)));
+    if (out->log_cmd_off) CK(L.out(s_lcoff, out->log_cmd_off));
+    CK(L.out(s_lop, out->log_op, lc));
+    CK(L.out(s_lkey, out->log_key, lc * 8));
+    CK(L.out(s_lval, out->log_val, lc * 8));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MPX_OK;
 }
 
 // ---- §8(f) ranks 3/4: instance-log encoding -------------------------------------------------

@@ -216,6 +216,20 @@ __attribute__((weak)) hipError_t launch_encode_accepts(
     int mode, int32_t nrep, const mpx_accept_batch* b, uint8_t* out, uint64_t out_cap,
     uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- Accept / Commit / PrepareReply payloads (mpx_unmarshal_frames; unmarshal.hip) ----------
+// Weak, like the proposer's. Scratch for calls of up to n_var frames carrying up to n_log
+// catch-up instances in total.
+__attribute__((weak)) uint64_t unmarshal_work_bytes(uint64_t n_var, uint64_t n_log,
+                                                    Carver&& c = Carver());
+// o: a host struct of device pointers; d_n_var (optional, device): min(*d_n_var, n_var) frames are
+// processed. log_scratch: the catch-up instances the scratch was sized for (work_bytes must cover
+// unmarshal_work_bytes(n_var, min(log_scratch, len / 9))). Never reads buf at or past len
+// rounded up to 16.
+__attribute__((weak)) hipError_t launch_unmarshal(
+    int mode, const uint8_t* buf, uint64_t len, const mpx_var_frame* var, uint64_t n_var,
+    const uint64_t* d_n_var, const mpx_unmarshal_out* o, mpx_unmarshal_result* res,
+    uint64_t log_scratch, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

@@ -14,6 +14,8 @@ Names and argument meaning follow the reference handlers they replace:
   encode_accept_replies <- replyAccept -> SendMsg: the AcceptReply frames per leader connection
   propose_handle      <- bareminpaxos / paxos  handlePropose (which proposals become an instance)
   encode_accepts      <- bcastAccept -> SendMsg: the Accept frames per peer connection
+  unmarshal_frames    <- Accept / Commit / PrepareReply.Unmarshal (+ Instance, Command) of the
+                         frames decode_stream found: records and SoA arrays
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -534,6 +536,56 @@ class Engine:
         self._check(self.lib.mpx_encode_accepts_dev(self.h, C.byref(batch), d_out, out_cap,
                                                     d_dest_off, stream),
                     "mpx_encode_accepts_dev")
+
+    # ---- Accept / Commit / PrepareReply payloads: Unmarshal in a batch -------------------------
+    def unmarshal_frames(self, buf, var, caps=None):
+        """buf: the bytes decode_stream framed; var: its VAR_FRAME records. Returns (arrays,
+        mpx_unmarshal_result): a dict of R.UNMARSHAL_ARRAYS, each trimmed to its count. caps
+        (optional): (accept, commit, cmd, log_inst, log_cmd) capacities, None = what the frames
+        need; arrays come back trimmed to min(count, capacity)."""
+        buf = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else \
+            _c(buf, np.uint8)
+        var = _c(var, R.VAR_FRAME)
+        n, nv = len(buf), len(var)
+        need = (int((var["code"] == R.PEER_ACCEPT).sum()), int((var["code"] == R.PEER_COMMIT).sum()),
+                int(var["n_cmds"].astype(np.int64).sum()), int(var["n_log"].astype(np.int64).sum()),
+                n // 17)
+        ca, cc, cm, cl, clm = [w if c is None else c for c, w in zip(caps or (None,) * 5, need)]
+        a = {"accepts": np.zeros(ca, R.ACCEPT_MSG), "accept_last_committed": np.zeros(ca, np.int32),
+             "commits": np.zeros(cc, R.ACCEPT_MSG), "cmd_off": np.zeros(nv + 1, np.uint64),
+             "op": np.zeros(cm, np.uint8), "key": np.zeros(cm, np.int64),
+             "val": np.zeros(cm, np.int64), "log_inst_off": np.zeros(nv + 1, np.uint64),
+             "log_recs": np.zeros(cl, R.LOG_REC), "log_cmd_off": np.zeros(cl + 1, np.uint64),
+             "log_op": np.zeros(clm, np.uint8), "log_key": np.zeros(clm, np.int64),
+             "log_val": np.zeros(clm, np.int64)}
+        out = _lib.MpxUnmarshalOut()
+        for name in R.UNMARSHAL_ARRAYS:
+            setattr(out, name, _ptr(a[name]) if len(a[name]) else None)
+        out.accept_cap, out.commit_cap, out.cmd_cap = ca, cc, cm
+        out.log_inst_cap, out.log_cmd_cap = cl, clm
+        res = np.zeros(1, R.UNMARSHAL_RESULT)
+        self._check(self.lib.mpx_unmarshal_frames(self.h, _ptr(buf), n, _ptr(var), nv,
+                                                  C.byref(out), _ptr(res)),
+                    "mpx_unmarshal_frames")
+        r = res[0]
+        na, nc = min(int(r["n_accepts"]), ca), min(int(r["n_commits"]), cc)
+        m, li = min(int(r["n_cmds"]), cm), min(int(r["n_log_inst"]), cl)
+        lm = min(int(r["n_log_cmds"]), clm)
+        trim = {"accepts": na, "accept_last_committed": na, "commits": nc, "op": m, "key": m,
+                "val": m, "log_recs": li, "log_cmd_off": li + 1, "log_op": lm, "log_key": lm,
+                "log_val": lm}
+        return {k: v[:trim.get(k, len(v))] for k, v in a.items()}, r
+
+    def unmarshal_frames_reserve(self, max_var, max_log_inst):
+        self._check(self.lib.mpx_unmarshal_frames_reserve(self.h, max_var, max_log_inst),
+                    "mpx_unmarshal_frames_reserve")
+
+    def unmarshal_frames_dev(self, d_buf, n, d_var, n_var, d_n_var, out, d_res, stream=None):
+        """out: _lib.MpxUnmarshalOut of device pointers; d_n_var: optional device u64 (the frame
+        count mpx_decode_stream_dev left); d_res: device mpx_unmarshal_result"""
+        self._check(self.lib.mpx_unmarshal_frames_dev(self.h, d_buf, n, d_var, n_var, d_n_var,
+                                                      C.byref(out), d_res, stream),
+                    "mpx_unmarshal_frames_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

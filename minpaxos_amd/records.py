@@ -116,6 +116,18 @@ PH_ACCEPT, PH_NOT_LEADER, PH_REFUSED, PH_PREPARE = 1, 2, 4, 8
 AB_THRIFTY = 1
 
 
+# mpx_unmarshal_frames: mpx_unmarshal_result, and the arrays of mpx_unmarshal_out in the order a
+# trimmed result carries them (engine.Engine.unmarshal_frames)
+UNMARSHAL_RESULT = np.dtype([("n_accepts", "<u8"), ("n_commits", "<u8"), ("n_cmds", "<u8"),
+                             ("n_log_inst", "<u8"), ("n_log_cmds", "<u8"), ("n_var", "<u8")])
+UNMARSHAL_ARRAYS = ("accepts", "accept_last_committed", "commits", "cmd_off", "op", "key", "val",
+                    "log_inst_off", "log_recs", "log_cmd_off", "log_op", "log_key", "log_val")
+# bytes from a variable-length frame's code byte to V(len(Command)), by mode and code
+VAR_HEADER = {MODE_MIN: {PEER_ACCEPT: 17, PEER_COMMIT: 13, PEER_PREPARE_REPLY: 18},
+              MODE_CLASSIC: {PEER_ACCEPT: 13, PEER_COMMIT: 13, PEER_PREPARE_REPLY: 10}}
+assert UNMARSHAL_RESULT.itemsize == 48
+
+
 def varint_len(x):
     """bytes of binary.PutVarint(x), x >= 0"""
     u, n = x << 1, 1
