@@ -43,6 +43,12 @@
  *                            statemarsh.go:21-39): the frames mpx_decode_stream found, as the
  *                            records mpx_accept_handle takes and the SoA commands and catch-up log
  *                            mpx_apply, mpx_encode_log and mpx_accept_batch.log_* take
+ *   mpx_commit_handle     <- bareminpaxos.(*Replica).handleCommit / handleCommitShort
+ *                            bareminpaxos.go:856-910 / paxos.go:522-575 with updateCommittedUpTo
+ *                            (paxos.go:259-264): the follower's last station of Phase 2, and
+ *                            mpx_encode_commits the CommitShort / Commit frames bcastCommit
+ *                            (bareminpaxos.go:565-615 / paxos.go:336-386) writes to every peer;
+ *                            mpx_gather_commit_shorts turns received CommitShort bodies into records
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -102,7 +108,8 @@ extern "C" {
                               8: + MPX_FLAG_STEP_ONE_LAUNCH; additive since, same number:
                               mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev],
                               mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev],
-                              mpx_unmarshal_frames[_reserve|_dev] */
+                              mpx_unmarshal_frames[_reserve|_dev], mpx_commit_handle[_dev],
+                              mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -978,6 +985,145 @@ int mpx_unmarshal_frames_reserve(mpx_engine* eng, size_t max_var, size_t max_log
 int mpx_unmarshal_frames_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
                              const mpx_var_frame* d_var, size_t n_var, const uint64_t* d_n_var,
                              const mpx_unmarshal_out* out, mpx_unmarshal_result* d_res, void* stream);
+
+/* ---- the commit side: batched handleCommit[Short] and the Commit bytes -----------------------
+ * The last station of Phase 2. A leader that decided an instance calls bcastCommit
+ * (bareminpaxos.go:565-615 / paxos.go:336-386); every follower runs
+ *   handleCommit       bareminpaxos.go:856-883 / paxos.go:522-549
+ *   handleCommitShort  bareminpaxos.go:885-910 / paxos.go:551-575
+ * per message and advances committedUpTo (updateCommittedUpTo, paxos.go:259-264). The two
+ * protocols' handlers are the same code and their wire formats are identical, so nothing here
+ * depends on mpx_config.mode. Instance numbers are window numbers as in mpx_accept_handle:
+ * idx = instance - inst_base belongs to group g = idx / ipg, n_inst == n_groups * ipg,
+ * first_g = inst_base + g * ipg and "nothing committed" is first_g - 1.                        */
+
+#define MPX_VALUE_KEEP 0xFFFFFFFFu /* value_id of a CommitShort record: the message carries no
+                                      Command; on a nil instance it is the handle of Cmds == nil */
+
+#define MPX_CH_INSTALLED 1u /* the instance was nil: a fresh Instance{ballot, COMMITTED} was made  */
+#define MPX_CH_CMDS 2u      /* a Commit: the host stores Command (and recordCommands)              */
+#define MPX_CH_REQUEUE 4u   /* clientProposals were pushed back on ProposeChan (:871-876 / :537-542) */
+
+/* msgs[n]: the record mpx_unmarshal_frames writes for Commits and mpx_gather_commit_shorts for
+ * CommitShorts, under the contract above (grouped by instance, ascending; slot order = arrival
+ * order). A CommitShort carries value_id == MPX_VALUE_KEEP, a Commit any other handle. leader_id
+ * is not read. st[n_inst] is updated in place; committed_upto[n_groups] (r.committedUpTo per
+ * group) is in/out. Outputs are slot-aligned with msgs, one entry per message, always written:
+ * effect[i] (MPX_CH_*) and, when log_recs is given, log_recs[i] = {ballot = msgs[i].ballot,
+ * status = COMMITTED, inst_no = msgs[i].instance, pad 0}: the record mpx_encode_log(
+ * MPX_LOG_DURABLE) takes for recordInstanceMetadata.
+ * Per message, sequentially in array order (no ballot is compared: a lower-ballot Commit
+ * overwrites, as in the Go):
+ *   instance  message      state after                                 effect
+ *   nil       Commit       {COMMITTED, ballot, value_id, 0}            INSTALLED | CMDS
+ *   nil       CommitShort  {COMMITTED, ballot, MPX_VALUE_KEEP, 0}      INSTALLED
+ *   non-nil   Commit       status COMMITTED, ballot, value_id taken    CMDS (| REQUEUE)
+ *   non-nil   CommitShort  status COMMITTED, ballot; value_id kept     0 (| REQUEUE)
+ * REQUEUE when flags has MPX_PF_HAS_PROPOSALS: that bit is cleared and MPX_PF_REQUEUED set (the
+ * acceptor's convention; the caller clears MPX_PF_REQUEUED once it has pushed the proposals back).
+ * committed_upto[g], for every group that has at least one message in the batch and only for
+ * those (the reference advances inside a handler): c rises while c + 1 < first_g + ipg and
+ * st[c + 1].status == COMMITTED, over the states the batch leaves. Inside a commit-only batch
+ * statuses only move to COMMITTED, so this equals calling updateCommittedUpTo after every
+ * message. The advance stops at the window's end, where the reference would index the next
+ * slot of instanceSpace.
+ * Errors: an instance outside the window -> MPX_E_NIL_INSTANCE; order -> MPX_E_INVAL; a
+ * committed_upto[g] outside [first_g - 1, first_g + ipg - 1] -> MPX_E_INVAL (the host form checks
+ * every group before anything runs; the _dev form reports it through the error word for the
+ * groups the batch touches).                                                                    */
+int mpx_commit_handle(mpx_engine* eng, const mpx_accept_msg* msgs, size_t n,
+                      mpx_acceptor_state* st, size_t n_inst, int32_t inst_base,
+                      int32_t* committed_upto, size_t n_groups, uint32_t ipg, uint8_t* effect,
+                      mpx_log_rec* log_recs);
+/* device form: d_st is in place (no in / out pair: the prefix reads the final states of instances
+ * that had no message); d_st[i] is stored only for instances that have messages. Two kernels on
+ * the stream, no scratch, no control words beyond the error word; it captures into a graph.
+ * Alignment: d_msgs, d_st, d_log_recs 16 bytes; d_committed_upto 4; d_effect any address.        */
+int mpx_commit_handle_dev(mpx_engine* eng, const mpx_accept_msg* d_msgs, size_t n,
+                          mpx_acceptor_state* d_st, size_t n_inst, int32_t inst_base,
+                          int32_t* d_committed_upto, size_t n_groups, uint32_t ipg,
+                          uint8_t* d_effect, mpx_log_rec* d_log_recs, void* stream);
+
+/* one decided instance whose Commit goes out: the leader fills the array from the tally's decided
+ * mask, with MPX_CS_SEND on the decided slots (the others are skipped: no compaction needed)    */
+typedef struct mpx_commit_send {
+    int32_t instance;
+    int32_t ballot;
+    uint64_t first_cmd; /* the instance's commands: [first_cmd, first_cmd + n_cmds) of cmd_*      */
+    uint32_t n_cmds;
+    uint32_t flags;     /* MPX_CS_*                                                               */
+    uint32_t pad[2];
+} mpx_commit_send; /* 32 B */
+#define MPX_CS_SEND 1u
+
+/* one call of mpx_encode_commits. groups: only self_id (LeaderId) is read. cmd_*: SoA, indexed by a
+ * send's first_cmd / n_cmds. flags: MPX_AB_THRIFTY. alive_mask: bit q = r.Alive[q].              */
+typedef struct mpx_commit_batch {
+    const mpx_commit_send* sends;
+    size_t n_sends;
+    int32_t inst_base;
+    uint32_t ipg;
+    size_t n_groups;
+    const mpx_proposer_group* groups;
+    const uint8_t* cmd_op;
+    const int64_t* cmd_key;
+    const int64_t* cmd_val;
+    size_t n_cmds;
+    uint32_t flags;
+    uint32_t alive_mask;
+} mpx_commit_batch;
+
+/* Destinations of a send, as bcastCommit's two loops walk the ring q = self_id + 1, ... mod N:
+ * the first n alive successors (n = N-1, or N>>1 with MPX_AB_THRIFTY) get a CommitShort; with
+ * MPX_AB_THRIFTY, when that loop did not wrap (q != self_id), the following alive successors get a
+ * full Commit until N-1 have been sent or the ring returns to self_id. N = 1 sends nothing.
+ * Frames, little endian, V = binary.PutVarint:
+ *   CommitShort 17 B  [11][LeaderId][Instance][Count = n_cmds][Ballot]
+ *                     (minpaxosprotomarsh.go:710-735 / paxosprotomarsh.go:465-490)
+ *   Commit            [10][LeaderId][Instance][Ballot][V(n)][n x 17 B]
+ *                     (minpaxosprotomarsh.go:618-646 / paxosprotomarsh.go:373-401)
+ * out receives, destination by destination, each destination's frames in send-array order, back
+ * to back; destination q's run is out[dest_off[q] .. dest_off[q+1]) (dest_off: N+1 entries, always
+ * complete). Nothing is ever written at or past out_cap.
+ * Errors, host form: a send outside the window, a command range outside its arrays, self_id
+ * outside [0, N) -> MPX_E_INVAL; dest_off[N] > out_cap -> MPX_E_INVAL with dest_off written.    */
+#define MPX_COMMIT_SHORT_FRAME 17
+int mpx_encode_commits(mpx_engine* eng, const mpx_commit_batch* b, uint8_t* out, size_t out_cap,
+                       uint64_t* dest_off);
+/* scratch of the family's _dev calls: mpx_encode_commits_dev of up to max_sends slots and
+ * mpx_gather_commit_shorts_dev of up to max_other frames (grows only). The scratch lives in the
+ * handle: like the other *_dev calls that keep scratch there, the family's calls on one handle run
+ * in one stream order, and a larger reserve invalidates graphs captured before it.              */
+int mpx_encode_commits_reserve(mpx_engine* eng, size_t max_sends, size_t max_other);
+/* b: a host struct of device pointers. The same errors are reported through the error word
+ * (MPX_E_INVAL at the next synchronising call) and such a send emits no frame. Never allocates or
+ * synchronises. Alignment: sends, groups 16 bytes; keys, values, d_dest_off 8; cmd_op and d_out
+ * any address.                                                                                  */
+int mpx_encode_commits_dev(mpx_engine* eng, const mpx_commit_batch* b, uint8_t* d_out,
+                           size_t out_cap, uint64_t* d_dest_off, void* stream);
+
+/* CommitShort bodies to records: from the mpx_peer_frame list mpx_decode_stream[_dev] left (the
+ * same buf, the same offsets), the frames of code MPX_PEER_COMMIT_SHORT, compacted and in stream
+ * order: msgs[i] = {instance, ballot, leader_id, value_id = MPX_VALUE_KEEP}, count[i] = the Count
+ * field, frame_index[i] = the frame's index in other (so the caller can merge with the
+ * unmarshalled Commits by stream offset). Frames of other codes are skipped. *n_shorts is always
+ * complete; nothing is written at or past cap (a capacity of 0 may come with null arrays).
+ * Host form: a CommitShort frame outside [0, len) -> MPX_E_INVAL.                               */
+int mpx_gather_commit_shorts(mpx_engine* eng, const uint8_t* buf, size_t len,
+                             const mpx_peer_frame* other, size_t n_other, mpx_accept_msg* msgs,
+                             int32_t* count, uint32_t* frame_index, size_t cap, uint64_t* n_shorts);
+/* device form: needs mpx_encode_commits_reserve(.., n_other) first. d_n_other (optional, device):
+ * min(*d_n_other, n_other) frames are processed, so the call can be captured right behind
+ * mpx_decode_stream_dev with n_other = other_cap and d_n_other = &d_stream_res->n_other. A frame
+ * outside [0, len) is reported through the error word and skipped. d_buf may be read up to len
+ * rounded up to 16, never at or past it. Alignment: d_buf 16 bytes, as for the decoders (any other
+ * address is rejected with MPX_E_INVAL); d_msgs 16; d_n_other, d_n_shorts 8; d_other, d_count,
+ * d_frame_index 4.                                                                              */
+int mpx_gather_commit_shorts_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
+                                 const mpx_peer_frame* d_other, size_t n_other,
+                                 const uint64_t* d_n_other, mpx_accept_msg* d_msgs,
+                                 int32_t* d_count, uint32_t* d_frame_index, size_t cap,
+                                 uint64_t* d_n_shorts, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

@@ -53,6 +53,13 @@ class MpxUnmarshalOut(C.Structure):
                 ("log_val", _p), ("log_cmd_cap", _sz)]
 
 
+class MpxCommitBatch(C.Structure):
+    _fields_ = [("sends", _p), ("n_sends", _sz), ("inst_base", C.c_int32), ("ipg", C.c_uint32),
+                ("n_groups", _sz), ("groups", _p), ("cmd_op", _p), ("cmd_key", _p),
+                ("cmd_val", _p), ("n_cmds", _sz), ("flags", C.c_uint32),
+                ("alive_mask", C.c_uint32)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -114,6 +121,15 @@ SIGNATURES = {
     "mpx_unmarshal_frames_reserve": (C.c_int, [_p, _sz, _sz]),
     "mpx_unmarshal_frames_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, C.POINTER(MpxUnmarshalOut),
                                            _p, _p]),
+    "mpx_commit_handle": (C.c_int, [_p, _p, _sz, _p, _sz, _i32, _p, _sz, C.c_uint32, _p, _p]),
+    "mpx_commit_handle_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _i32, _p, _sz, C.c_uint32, _p, _p,
+                                        _p]),
+    "mpx_encode_commits": (C.c_int, [_p, C.POINTER(MpxCommitBatch), _p, _sz, _p]),
+    "mpx_encode_commits_reserve": (C.c_int, [_p, _sz, _sz]),
+    "mpx_encode_commits_dev": (C.c_int, [_p, C.POINTER(MpxCommitBatch), _p, _sz, _p, _p]),
+    "mpx_gather_commit_shorts": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _sz, _p]),
+    "mpx_gather_commit_shorts_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _p, _sz, _p,
+                                               _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

@@ -73,8 +73,9 @@ struct mpx_engine {
     bool kv_ready = false;
     // the families' scratch: grown by the host forms and the *_reserve calls, never by a _dev form
     DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work, are_work, ab_work,
-        um_work;
+        um_work, cm_work;
     size_t um_var_cap = 0, um_log_cap = 0;  // what um_work was last sized for (mpx_unmarshal_frames)
+    size_t cm_send_cap = 0, cm_other_cap = 0;  // ... and cm_work (mpx_encode_commits_reserve)
     mpx::ApplyOpts apply{};  // mpx_config.apply_* (fixed for the handle's life)
     // replica-sized mpx_apply calls: pinned, GPU-mapped staging the one-launch kernel reads the
     // commands from and writes the results to (no DMA copies on the call's path)
@@ -392,7 +393,7 @@ int mpx_close(mpx_engine* e) {
     if (e->comm) ncclCommDestroy(e->comm);
     for (DevBuf* x : {&e->arena, &e->apply_work, &e->decode_work, &e->stream_work, &e->fan_work,
                       &e->log_work, &e->replay_work, &e->are_work, &e->ab_work, &e->um_work,
-                      &e->worklist})
+                      &e->cm_work, &e->worklist})
         if (x->p) (void)hipFree(x->p);
     if (e->pin_io.p) (void)hipHostFree(e->pin_io.p);
     if (e->pin_staged.p) (void)hipHostFree(e->pin_staged.p);
@@ -1714,6 +1715,221 @@ int mpx_unmarshal_frames(mpx_engine* e, const uint8_t* buf, size_t len, const mp
     CK(L.out(s_lval, out->log_val, lc * 8));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return MPX_OK;
+}
+
+// ---- the commit side: handleCommit[Short], the Commit bytes, CommitShort records --------------
+// (weak launchers, like the proposer's)
+namespace {
+const char* const kNoCommit = "the commit kernels are not built in";
+
+// the sizes the host and _dev forms of the family share
+int commit_limits(mpx_engine* e, size_t n, size_t n_groups, size_t n_inst, uint32_t ipg) {
+    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
+        n_inst > (1ull << 32))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    return record_limit(e, n);
+}
+int commit_batch_args(mpx_engine* e, const mpx_commit_batch* b, const void* out, size_t out_cap,
+                      const void* dest_off) {
+    if (!b || !dest_off || (out_cap && !out) || (b->n_sends && (!b->sends || !b->groups)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    if (b->n_sends || b->n_groups)
+        CK(commit_limits(e, b->n_sends, b->n_groups, b->n_groups * (size_t)b->ipg, b->ipg));
+    return MPX_OK;
+}
+int gather_args(mpx_engine* e, const void* buf, size_t len, const void* other, size_t n_other,
+                const void* msgs, const void* count, const void* fidx, size_t cap,
+                const void* n_shorts) {
+    if (!n_shorts || (len && !buf) || (n_other && (!other || !len)) ||
+        (cap && (!msgs || !count || !fidx)))
+        return fail(e, MPX_E_INVAL, "null argument");
+    CK(decode_limit(e, len));
+    return record_limit(e, n_other);
+}
+}  // namespace
+
+int mpx_commit_handle_dev(mpx_engine* e, const mpx_accept_msg* d_msgs, size_t n,
+                          mpx_acceptor_state* d_st, size_t n_inst, int32_t inst_base,
+                          int32_t* d_committed_upto, size_t n_groups, uint32_t ipg,
+                          uint8_t* d_effect, mpx_log_rec* d_log_recs, void* stream) {
+    if (!e) return MPX_E_INVAL;
+    if ((n && (!d_msgs || !d_effect)) || !d_st || !d_committed_upto)
+        return fail(e, MPX_E_INVAL, "null argument");
+    CK(commit_limits(e, n, n_groups, n_inst, ipg));
+    if (!mpx::launch_commit_handle)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_commit_handle: ") + kNoCommit);
+    HIPCHK(e, mpx::launch_commit_handle(d_msgs, n, d_st, n_inst, inst_base, d_committed_upto,
+                                        n_groups, ipg, d_effect, d_log_recs, e->d_err,
+                                        pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_commit_handle(mpx_engine* e, const mpx_accept_msg* msgs, size_t n, mpx_acceptor_state* st,
+                      size_t n_inst, int32_t inst_base, int32_t* committed_upto, size_t n_groups,
+                      uint32_t ipg, uint8_t* effect, mpx_log_rec* log_recs) {
+    if (!e) return MPX_E_INVAL;
+    if ((n && (!msgs || !effect)) || !st || !committed_upto)
+        return fail(e, MPX_E_INVAL, "null argument");
+    CK(commit_limits(e, n, n_groups, n_inst, ipg));
+    for (size_t g = 0; g < n_groups; ++g) {
+        const int64_t first = (int64_t)inst_base + (int64_t)(g * ipg);
+        if (committed_upto[g] < first - 1 || committed_upto[g] > first + (int64_t)ipg - 1)
+            return fail(e, MPX_E_INVAL, "committed_upto[g] outside [first_g - 1, first_g + ipg - 1]");
+    }
+    if (!mpx::launch_commit_handle)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_commit_handle: ") + kNoCommit);
+    CK(begin(e));
+    Stage L(e);
+    const Slot s_msg = L.add(n * sizeof(mpx_accept_msg)),
+               s_st = L.add(n_inst * sizeof(mpx_acceptor_state)),
+               s_cu = L.add(n_groups * sizeof(int32_t)), s_eff = L.add(n),
+               s_log = L.add(log_recs ? n * sizeof(mpx_log_rec) : 0);
+    CK(L.commit());
+    CK(L.in(s_msg, msgs));
+    CK(L.in(s_st, st));
+    CK(L.in(s_cu, committed_upto));
+    CK(mpx_commit_handle_dev(e, L.at<mpx_accept_msg>(s_msg), n, L.at<mpx_acceptor_state>(s_st),
+                             n_inst, inst_base, L.at<int32_t>(s_cu), n_groups, ipg,
+                             L.at<uint8_t>(s_eff), L.at<mpx_log_rec>(s_log, log_recs), e->stream));
+    CK(L.out(s_st, st));
+    CK(L.out(s_cu, committed_upto));
+    CK(L.out(s_eff, effect));
+    if (log_recs) CK(L.out(s_log, log_recs));
+    return finish(e);
+}
+
+int mpx_encode_commits_reserve(mpx_engine* e, size_t max_sends, size_t max_other) {
+    if (!e) return MPX_E_INVAL;
+    CK(record_limit(e, max_sends));
+    CK(record_limit(e, max_other));
+    if (!mpx::commits_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
+    e->cm_send_cap = std::max(e->cm_send_cap, max_sends);
+    e->cm_other_cap = std::max(e->cm_other_cap, max_other);
+    return reserve(e, e->cm_work, mpx::commits_work_bytes((uint32_t)e->cfg.n_replicas,
+                                                          e->cm_send_cap, e->cm_other_cap));
+}
+
+int mpx_encode_commits_dev(mpx_engine* e, const mpx_commit_batch* b, uint8_t* d_out, size_t out_cap,
+                           uint64_t* d_dest_off, void* stream) {
+    if (!e) return MPX_E_INVAL;
+    CK(commit_batch_args(e, b, d_out, out_cap, d_dest_off));
+    if (!mpx::launch_encode_commits || !mpx::commits_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
+    // (an empty call uses no scratch)
+    CK(reserved(e, e->cm_work,
+                b->n_sends ? mpx::commits_work_bytes((uint32_t)e->cfg.n_replicas, b->n_sends, 0) : 0,
+                "mpx_encode_commits_dev", "mpx_encode_commits_reserve(n_sends, 0)"));
+    HIPCHK(e, mpx::launch_encode_commits(e->cfg.n_replicas, b, d_out, out_cap, d_dest_off,
+                                         e->cm_work.p, e->cm_work.cap, e->d_err, pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_encode_commits(mpx_engine* e, const mpx_commit_batch* b, uint8_t* out, size_t out_cap,
+                       uint64_t* dest_off) {
+    if (!e) return MPX_E_INVAL;
+    CK(commit_batch_args(e, b, out, out_cap, dest_off));
+    const int32_t N = e->cfg.n_replicas;
+    const size_t n_inst = b->n_groups * (size_t)b->ipg;
+    // the device kernels report these through the error word; here they answer before any launch
+    for (size_t s = 0; s < b->n_sends; ++s) {
+        const mpx_commit_send& x = b->sends[s];
+        if (!(x.flags & MPX_CS_SEND)) continue;
+        const int64_t idx = (int64_t)x.instance - b->inst_base;
+        if (idx < 0 || (uint64_t)idx >= n_inst)
+            return fail(e, MPX_E_INVAL, "a send names an instance outside the window");
+        if (x.first_cmd > b->n_cmds || x.n_cmds > b->n_cmds - x.first_cmd ||
+            (x.n_cmds && (!b->cmd_op || !b->cmd_key || !b->cmd_val)))
+            return fail(e, MPX_E_INVAL, "a send's commands are outside the command arrays");
+        const int32_t self = b->groups[(size_t)idx / b->ipg].self_id;
+        if (self < 0 || self >= N) return fail(e, MPX_E_INVAL, "self_id outside [0, N)");
+    }
+    if (!mpx::launch_encode_commits || !mpx::commits_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
+    CK(begin(e));
+    if (b->n_sends) GROW(e, e->cm_work, mpx::commits_work_bytes((uint32_t)N, b->n_sends, 0));
+    Stage L(e);
+    const size_t m = b->n_cmds;
+    const Slot s_snd = L.add(b->n_sends * sizeof(mpx_commit_send)),
+               s_grp = L.add(b->n_sends ? b->n_groups * sizeof(mpx_proposer_group) : 0),
+               s_op = L.add(b->cmd_op ? m : 0), s_key = L.add(b->cmd_key ? m * 8 : 0),
+               s_val = L.add(b->cmd_val ? m * 8 : 0), s_out = L.add(out_cap),
+               s_off = L.add(((size_t)N + 1) * 8);
+    CK(L.commit());
+    CK(L.in(s_snd, b->sends));
+    CK(L.in(s_grp, b->groups));
+    CK(L.in(s_op, b->cmd_op));
+    CK(L.in(s_key, b->cmd_key));
+    CK(L.in(s_val, b->cmd_val));
+    mpx_commit_batch d = *b;
+    d.sends = L.at<mpx_commit_send>(s_snd);
+    d.groups = L.at<mpx_proposer_group>(s_grp);
+    d.cmd_op = L.at<uint8_t>(s_op);
+    d.cmd_key = L.at<int64_t>(s_key);
+    d.cmd_val = L.at<int64_t>(s_val);
+    CK(mpx_encode_commits_dev(e, &d, L.at<uint8_t>(s_out), out_cap, L.at<uint64_t>(s_off),
+                              e->stream));
+    CK(L.out(s_off, dest_off));
+    CK(finish(e));
+    if (dest_off[N] > out_cap) return fail(e, MPX_E_INVAL, "out_cap is smaller than the frames");
+    CK(L.out(s_out, out, dest_off[N]));
+    return finish(e);
+}
+
+int mpx_gather_commit_shorts_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
+                                 const mpx_peer_frame* d_other, size_t n_other,
+                                 const uint64_t* d_n_other, mpx_accept_msg* d_msgs, int32_t* d_count,
+                                 uint32_t* d_frame_index, size_t cap, uint64_t* d_n_shorts,
+                                 void* stream) {
+    if (!e) return MPX_E_INVAL;
+    CK(gather_args(e, d_buf, len, d_other, n_other, d_msgs, d_count, d_frame_index, cap,
+                   d_n_shorts));
+    if ((uintptr_t)d_buf & 15)
+        return fail(e, MPX_E_INVAL, "mpx_gather_commit_shorts_dev: d_buf must be 16-byte aligned");
+    if (!mpx::launch_gather_commit_shorts || !mpx::commits_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_gather_commit_shorts: ") + kNoCommit);
+    CK(reserved(e, e->cm_work, n_other ? mpx::commits_work_bytes(1, 0, n_other) : 0,
+                "mpx_gather_commit_shorts_dev", "mpx_encode_commits_reserve(0, n_other)"));
+    HIPCHK(e, mpx::launch_gather_commit_shorts(d_buf, len, d_other, n_other, d_n_other, d_msgs,
+                                               d_count, d_frame_index, cap, d_n_shorts,
+                                               e->cm_work.p, e->cm_work.cap, e->d_err,
+                                               pick(e, stream)));
+    return MPX_OK;
+}
+
+int mpx_gather_commit_shorts(mpx_engine* e, const uint8_t* buf, size_t len,
+                             const mpx_peer_frame* other, size_t n_other, mpx_accept_msg* msgs,
+                             int32_t* count, uint32_t* frame_index, size_t cap, uint64_t* n_shorts) {
+    if (!e) return MPX_E_INVAL;
+    CK(gather_args(e, buf, len, other, n_other, msgs, count, frame_index, cap, n_shorts));
+    uint64_t want = 0;  // the device kernel reports a frame outside the buffer and skips it
+    for (size_t i = 0; i < n_other; ++i) {
+        if (other[i].code != MPX_PEER_COMMIT_SHORT) continue;
+        if ((uint64_t)other[i].offset + MPX_COMMIT_SHORT_FRAME > len)
+            return fail(e, MPX_E_INVAL, "a CommitShort frame lies outside [0, len)");
+        ++want;
+    }
+    if (!mpx::launch_gather_commit_shorts || !mpx::commits_work_bytes)
+        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_gather_commit_shorts: ") + kNoCommit);
+    CK(begin(e));
+    if (n_other) GROW(e, e->cm_work, mpx::commits_work_bytes(1, 0, n_other));
+    const size_t k = std::min<uint64_t>(cap, want);
+    Stage L(e);
+    const Slot s_buf = L.add(len), s_oth = L.add(n_other * sizeof(mpx_peer_frame)),
+               s_msg = L.add(k * sizeof(mpx_accept_msg)), s_cnt = L.add(k * 4),
+               s_idx = L.add(k * 4), s_n = L.add(sizeof(uint64_t));
+    CK(L.commit());
+    CK(L.in(s_buf, buf));
+    CK(L.in(s_oth, other));
+    CK(mpx_gather_commit_shorts_dev(e, L.at<uint8_t>(s_buf), len, L.at<mpx_peer_frame>(s_oth),
+                                    n_other, nullptr, L.at<mpx_accept_msg>(s_msg),
+                                    L.at<int32_t>(s_cnt), L.at<uint32_t>(s_idx), k,
+                                    L.at<uint64_t>(s_n), e->stream));
+    CK(L.out(s_n, n_shorts));
+    CK(L.out(s_msg, msgs));
+    CK(L.out(s_cnt, count));
+    CK(L.out(s_idx, frame_index));
+    return finish(e);
 }
 
 // ---- §8(f) ranks 3/4: instance-log encoding -------------------------------------------------

@@ -230,6 +230,30 @@ __attribute__((weak)) hipError_t launch_unmarshal(
     const uint64_t* d_n_var, const mpx_unmarshal_out* o, mpx_unmarshal_result* res,
     uint64_t log_scratch, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- the commit side (mpx_commit_handle, mpx_encode_commits, mpx_gather_commit_shorts;
+// commit.hip) -------------------------------------------------------------------------------
+// Weak, like the proposer's. The handler is two launches (the handlers, then the per-group
+// committedUpTo prefix over the states they left): no scratch, no control words.
+__attribute__((weak)) hipError_t launch_commit_handle(
+    const mpx_accept_msg* msgs, uint64_t n, mpx_acceptor_state* st, uint64_t n_inst, int32_t base,
+    int32_t* committed_upto, uint64_t n_groups, uint32_t ipg, uint8_t* effect, mpx_log_rec* log_recs,
+    uint32_t* err, hipStream_t stream);
+// the family's scratch: an encode of n_sends slots to nrep destinations, a gather over n_other
+// frames (each launcher carves with its own call's sizes and 0 for the other's)
+__attribute__((weak)) uint64_t commits_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_other,
+                                                  Carver&& c = Carver());
+// b: a host struct of device pointers; nothing is written at or past out + out_cap
+__attribute__((weak)) hipError_t launch_encode_commits(
+    int32_t nrep, const mpx_commit_batch* b, uint8_t* out, uint64_t out_cap, uint64_t* dest_off,
+    void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+// d_n_other (optional, device): min(*d_n_other, n_other) frames are processed. Never reads buf at
+// or past len rounded up to 16.
+__attribute__((weak)) hipError_t launch_gather_commit_shorts(
+    const uint8_t* buf, uint64_t len, const mpx_peer_frame* other, uint64_t n_other,
+    const uint64_t* d_n_other, mpx_accept_msg* msgs, int32_t* count, uint32_t* frame_index,
+    uint64_t cap, uint64_t* n_shorts, void* work, uint64_t work_bytes, uint32_t* err,
+    hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

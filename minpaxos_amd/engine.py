@@ -16,6 +16,10 @@ Names and argument meaning follow the reference handlers they replace:
   encode_accepts      <- bcastAccept -> SendMsg: the Accept frames per peer connection
   unmarshal_frames    <- Accept / Commit / PrepareReply.Unmarshal (+ Instance, Command) of the
                          frames decode_stream found: records and SoA arrays
+  commit_handle       <- bareminpaxos / paxos  handleCommit, handleCommitShort and
+                         updateCommittedUpTo for a commit-only batch
+  encode_commits      <- bcastCommit -> SendMsg: the CommitShort / Commit frames per peer
+  gather_commit_shorts <- CommitShort.Unmarshal of the frames decode_stream listed
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -586,6 +590,91 @@ class Engine:
         self._check(self.lib.mpx_unmarshal_frames_dev(self.h, d_buf, n, d_var, n_var, d_n_var,
                                                       C.byref(out), d_res, stream),
                     "mpx_unmarshal_frames_dev")
+
+    # ---- the commit side: handleCommit[Short], the Commit bytes, CommitShort records -----------
+    def commit_handle(self, msgs, st, committed_upto, inst_base=0, ipg=None, want_log=True):
+        """msgs: ACCEPT_MSG grouped by instance, ascending (value_id R.VALUE_KEEP = CommitShort);
+        st: ACCEPTOR_STATE of the window (copied); committed_upto: int32 per group (copied).
+        Returns (st, committed_upto, effect uint8[n], log_recs LOG_REC[n] or None)."""
+        msgs = _c(msgs, R.ACCEPT_MSG)
+        st = np.array(st, dtype=R.ACCEPTOR_STATE, copy=True)
+        cu = np.array(np.atleast_1d(committed_upto), dtype=np.int32, copy=True)
+        n, G = len(msgs), len(cu)
+        ipg = (len(st) // G if G else 0) if ipg is None else ipg
+        eff = np.zeros(max(n, 1), np.uint8)
+        log = np.zeros(max(n, 1), R.LOG_REC) if want_log else None
+        rc = self.lib.mpx_commit_handle(self.h, _ptr(msgs), n, _ptr(st), len(st), inst_base,
+                                        _ptr(cu), G, ipg, _ptr(eff), _ptr(log))
+        self._check(rc, "mpx_commit_handle")
+        return st, cu, eff[:n], (log[:n] if want_log else None)
+
+    def commit_handle_dev(self, d_msgs, n, d_st, n_inst, inst_base, d_committed_upto, n_groups,
+                          ipg, d_effect, d_log_recs=None, stream=None):
+        rc = self.lib.mpx_commit_handle_dev(self.h, d_msgs, n, d_st, n_inst, inst_base,
+                                            d_committed_upto, n_groups, ipg, d_effect, d_log_recs,
+                                            stream)
+        self._check(rc, "mpx_commit_handle_dev")
+
+    def encode_commits(self, sends, groups, cmds, inst_base=0, ipg=1, thrifty=False,
+                       alive_mask=0xFFFF, out_cap=None):
+        """sends: COMMIT_SEND (slots without R.CS_SEND are skipped); groups: PROPOSER_GROUP (only
+        self_id is read), group g owning window indices [g*ipg, (g+1)*ipg); cmds: (op, key, val).
+        Returns (bytes uint8, dest_off u64[N+1]): peer q's connection receives
+        out[dest_off[q]:dest_off[q+1]], CommitShort and Commit frames in send order."""
+        sends = _c(sends, R.COMMIT_SEND)
+        groups = _c(np.atleast_1d(groups), R.PROPOSER_GROUP)
+        op, key, val = _c(cmds[0], np.uint8), _c(cmds[1], np.int64), _c(cmds[2], np.int64)
+        N = self.n_replicas
+        b = _lib.MpxCommitBatch()
+        b.sends, b.n_sends, b.inst_base, b.ipg = _ptr(sends), len(sends), inst_base, ipg
+        b.groups, b.n_groups = _ptr(groups), len(groups)
+        b.cmd_op, b.cmd_key, b.cmd_val, b.n_cmds = _ptr(op), _ptr(key), _ptr(val), len(op)
+        b.flags = R.AB_THRIFTY if thrifty else 0
+        b.alive_mask = alive_mask
+        if out_cap is None:  # every send as a full Commit to every peer
+            sel = sends[(sends["flags"] & R.CS_SEND) != 0]
+            out_cap = int((18 * len(sel) + 17 * int(sel["n_cmds"].sum())) * N)
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        off = np.zeros(N + 1, np.uint64)
+        rc = self.lib.mpx_encode_commits(self.h, C.byref(b), _ptr(out), out_cap, _ptr(off))
+        self._check(rc, "mpx_encode_commits")
+        return out[:int(off[-1])], off
+
+    def encode_commits_reserve(self, max_sends, max_other=0):
+        self._check(self.lib.mpx_encode_commits_reserve(self.h, max_sends, max_other),
+                    "mpx_encode_commits_reserve")
+
+    def encode_commits_dev(self, batch, d_out, out_cap, d_dest_off, stream=None):
+        """batch: _lib.MpxCommitBatch of device pointers"""
+        self._check(self.lib.mpx_encode_commits_dev(self.h, C.byref(batch), d_out, out_cap,
+                                                    d_dest_off, stream),
+                    "mpx_encode_commits_dev")
+
+    def gather_commit_shorts(self, buf, other, cap=None):
+        """buf: the bytes decode_stream framed; other: its PEER_FRAME records. Returns (msgs
+        ACCEPT_MSG, count int32, frame_index uint32, n_shorts): the CommitShort frames in stream
+        order, trimmed to min(n_shorts, cap)."""
+        buf = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else \
+            _c(buf, np.uint8)
+        other = _c(other, R.PEER_FRAME)
+        cap = int((other["code"] == R.PEER_COMMIT_SHORT).sum()) if cap is None else cap
+        msgs = np.zeros(max(cap, 1), R.ACCEPT_MSG)
+        cnt = np.zeros(max(cap, 1), np.int32)
+        idx = np.zeros(max(cap, 1), np.uint32)
+        ns = np.zeros(1, np.uint64)
+        rc = self.lib.mpx_gather_commit_shorts(self.h, _ptr(buf), len(buf), _ptr(other),
+                                               len(other), _ptr(msgs), _ptr(cnt), _ptr(idx), cap,
+                                               _ptr(ns))
+        self._check(rc, "mpx_gather_commit_shorts")
+        k = min(int(ns[0]), cap)
+        return msgs[:k], cnt[:k], idx[:k], int(ns[0])
+
+    def gather_commit_shorts_dev(self, d_buf, n, d_other, n_other, d_n_other, d_msgs, d_count,
+                                 d_frame_index, cap, d_n_shorts, stream=None):
+        self._check(self.lib.mpx_gather_commit_shorts_dev(self.h, d_buf, n, d_other, n_other,
+                                                          d_n_other, d_msgs, d_count,
+                                                          d_frame_index, cap, d_n_shorts, stream),
+                    "mpx_gather_commit_shorts_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

@@ -115,6 +115,21 @@ PROPOSE_MAX_BATCH = 5000
 PH_ACCEPT, PH_NOT_LEADER, PH_REFUSED, PH_PREPARE = 1, 2, 4, 8
 AB_THRIFTY = 1
 
+# the commit side (mpx_commit_handle / mpx_encode_commits / mpx_gather_commit_shorts)
+VALUE_KEEP = 0xFFFFFFFF  # value_id of a CommitShort record (no Command; nil Cmds on a nil instance)
+CH_INSTALLED, CH_CMDS, CH_REQUEUE = 1, 2, 4
+# mpx_commit_send  <- one decided instance whose Commit goes out (CS_SEND: not skipped)
+COMMIT_SEND = np.dtype([("instance", "<i4"), ("ballot", "<i4"), ("first_cmd", "<u8"),
+                        ("n_cmds", "<u4"), ("flags", "<u4"), ("pad", "<u4", (2,))])
+CS_SEND = 1
+COMMIT_SHORT_FRAME = 17
+assert COMMIT_SEND.itemsize == 32
+
+
+def commit_frame_bytes(n_cmds):
+    """one full Commit on a peer connection (code byte + Marshal)"""
+    return 13 + varint_len(n_cmds) + 17 * n_cmds
+
 
 # mpx_unmarshal_frames: mpx_unmarshal_result, and the arrays of mpx_unmarshal_out in the order a
 # trimmed result carries them (engine.Engine.unmarshal_frames)

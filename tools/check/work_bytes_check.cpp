@@ -117,6 +117,9 @@ int main(int argc, char** argv) {
     family("accept_replies", S, true, SIZE_OF(accept_replies_work_bytes, x));
     family("unmarshal (n, n_log = n)", S, true, SIZE_OF(unmarshal_work_bytes, x, x));
     family("unmarshal (n = 1000, n_log)", S, true, SIZE_OF(unmarshal_work_bytes, 1000, x));
+    family("commits (N = 5, sends, other = 0)", S, true, SIZE_OF(commits_work_bytes, 5, x, 0));
+    family("commits (N = 16, sends = other)", S, true, SIZE_OF(commits_work_bytes, 16, x, x));
+    family("commits (sends = 0, other)", S, true, SIZE_OF(commits_work_bytes, 1, 0, x));
     family("logenc (n, m = 4n)", S, true, SIZE_OF(logenc_work_bytes, x, 4 * x));
     family("logenc (n = 1000, m)", S, true, SIZE_OF(logenc_work_bytes, 1000, x));
     for (const int32_t cap : {1, 8192, 1 << 20, 1 << 24, 1 << 25}) {
