@@ -13,6 +13,8 @@
 // tile's outputs as coalesced stores. Records at the head of a tile that continue an instance of
 // an earlier tile (the overhang) are answered by the lane that owns that instance, straight to
 // global memory, so a tile writes [first head, end). One launch, no scalars, no control words.
+// The speculative state preload and the round counter are tile.hpp's TileState, shared with
+// k_commit_handle; the wave-uniform trip count, s_to and the tile epilogue are its own.
 //
 // mpx_encode_accept_replies: a stable partition of the replies over at most MPX_MAX_REPLICAS
 // destinations fused with the encoding of the frames replyAccept -> SendMsg writes
@@ -26,7 +28,11 @@
 //                 frames into an LDS image grouped by destination, and copies every destination's
 //                 run to its place with 16-byte stores at 16-byte aligned addresses (the run's two
 //                 ends bytewise)
+// The partition's steps (dest_count_*, unit_count, unit_prefix, copy_run_shifted) are
+// frames.hpp's, shared with the CommitShort path of commit.hip; the frame encoding and the
+// dest_off rule are here.
 #include "common.hpp"
+#include "frames.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
 #include "tile.hpp"
@@ -106,14 +112,8 @@ __launch_bounds__(kTileBlock) void k_accept_handle(
     const int4* m4 = reinterpret_cast<const int4*>(msgs);
     const int4* s4 = reinterpret_cast<const int4*>(st_in);
     int4* out4 = reinterpret_cast<int4*>(replies);
-    int64_t spec_idx = -1;  // the state loaded ahead for round 0 (tile_walk's pre)
-    int4 spec = make_int4(0, 0, 0, 0);
-    uint32_t round = 0;     // rounds of the current tile done by this thread
-    auto pre = [&](int32_t inst0) {
-        round = 0;
-        spec_idx = (int64_t)inst0 - base + t;
-        if (spec_idx >= 0 && (uint64_t)spec_idx < n_inst) spec = ld_stream(s4 + spec_idx);
-    };
+    TileState ts;
+    auto pre = [&](int32_t inst0) { ts.preload(s4, inst0, base, n_inst, t); };
     tile_walk(S, m4, n, err, pre, [&](uint32_t a, uint32_t cnt, uint64_t after, uint64_t oend,
                                       bool own, int64_t, bool) {
         const int32_t inst = own ? S.rec[a].x : 0;
@@ -123,9 +123,7 @@ __launch_bounds__(kTileBlock) void k_accept_handle(
         int2 grp = make_int2(0, 0);
         if (inwin)
             grp = *reinterpret_cast<const int2*>(groups + (one_group ? 0u : (uint32_t)idx / ipg));
-        int4 st = inwin ? (idx == spec_idx ? spec : ld_stream(s4 + idx))
-                        : make_int4(MPX_STATUS_NIL, 0, 0, 0);
-        spec_idx = -1;  // (later rounds of the tile load their own)
+        int4 st = ts.take(s4, inwin, idx);
         auto answer = [&](int4 m) {
             AhOut o{make_int4(0, 0, 0, 0), -1, 0u};
             if (inwin) o = ah_step<MODE>(st, m, grp.x, grp.y);
@@ -161,8 +159,7 @@ __launch_bounds__(kTileBlock) void k_accept_handle(
         }
         if (inwin) st_stream(reinterpret_cast<int4*>(st_out) + idx, st);
         // after the tile's last round: the tile's outputs [first head, end), coalesced
-        ++round;
-        if (round * kTileBlock < S.nh) return;  // (uniform: nh is the workgroup's)
+        if (!ts.last_round(S)) return;
         __syncthreads();
         const uint64_t p0 = ((after - 1) / kTileRecs) * kTileRecs;
         const uint32_t end = (uint32_t)(after - p0), h0 = S.hpos[0];
@@ -217,12 +214,11 @@ hipError_t launch_accept_handle(int mode, const mpx_accept_msg* msgs, uint64_t n
 
 // ---- the reply bytes -----------------------------------------------------------------------------
 namespace {
-constexpr int kArBlock = 256;
+constexpr int kArBlock = kFrBlock;
 constexpr int kArWaves = kArBlock / kWave;           // 4
-constexpr int kArPer = 4;                            // replies per lane per tile
-constexpr int kArTile = kArBlock * kArPer;           // 1024 replies per tile
-constexpr int kArUnits = kArPer * kArWaves;          // (register k, wave) units, in array order
-constexpr int kArDest = MPX_MAX_REPLICAS;
+constexpr int kArPer = kFrPer;                       // replies per lane per tile
+constexpr int kArTile = kFrTile;                     // 1024 replies per tile
+constexpr int kArDest = kFrDest;
 
 struct ArHistIn {
     const uint32_t* h;
@@ -255,21 +251,14 @@ __global__ __launch_bounds__(kArBlock) void k_ar_count(const int32_t* __restrict
                                                        uint32_t* __restrict__ hist, uint32_t* err) {
     __shared__ uint32_t cnt[kArDest];
     const int t = threadIdx.x, l = lane_id();
-    if (t < kArDest) cnt[t] = 0;
-    __syncthreads();
+    dest_count_begin(cnt, t);
     const uint64_t p0 = (uint64_t)blockIdx.x * kArTile;
     uint32_t mine = 0;  // lane d < n_dest: replies of the wave to destination d
 #pragma unroll
-    for (int k = 0; k < kArPer; ++k) {
-        const uint32_t d = ar_dest(reply_to, n, p0 + k * kArBlock + t, n_dest, err);
-        for (uint32_t x = 0; x < n_dest; ++x) {
-            const uint32_t c = (uint32_t)popc(ballot(d == x));
-            mine += (uint32_t)l == x ? c : 0u;
-        }
-    }
-    if ((uint32_t)l < n_dest && mine) atomicAdd(&cnt[l], mine);
-    __syncthreads();
-    if ((uint32_t)t < n_dest) hist[(uint64_t)t * tiles + blockIdx.x] = cnt[t];
+    for (int k = 0; k < kArPer; ++k)
+        mine = dest_count_wave<kDestIndex>(
+            mine, ar_dest(reply_to, n, p0 + k * kArBlock + t, n_dest, err), n_dest, l);
+    dest_count_end(cnt, mine, n_dest, tiles, hist, t, l);
 }
 
 template <int FRAME>
@@ -279,7 +268,7 @@ __global__ __launch_bounds__(kArBlock) void k_ar_emit(
     uint64_t* __restrict__ dest_off, uint32_t* err) {
     // the tile's frames grouped by destination; 16 spare bytes for the last run's shifted reads
     __shared__ __attribute__((aligned(16))) uint8_t img[kArTile * FRAME + 16];
-    __shared__ uint16_t wc[kArUnits][kArDest];  // per (k, wave) unit: count, then exclusive prefix
+    __shared__ uint16_t wc[kFrUnits][kArDest];  // per (k, wave) unit: count, then exclusive prefix
     __shared__ uint32_t tstart[kArDest + 1];    // destination's first frame in the image
     const int t = threadIdx.x, l = lane_id(), w = t / kWave;
     const uint64_t p0 = (uint64_t)blockIdx.x * kArTile;
@@ -295,25 +284,11 @@ __global__ __launch_bounds__(kArBlock) void k_ar_emit(
     // stable rank inside the (k, wave) unit, and the unit's counts
 #pragma unroll
     for (int k = 0; k < kArPer; ++k) {
-        uint64_t own = 0;
-        for (uint32_t x = 0; x < n_dest; ++x) {
-            const uint64_t m = ballot(dst[k] == x);
-            own = dst[k] == x ? m : own;
-            if ((uint32_t)l == x) wc[k * kArWaves + w][x] = (uint16_t)popc(m);
-        }
+        const uint64_t own = unit_count<kDestIndex>(wc[k * kArWaves + w], dst[k], n_dest, l);
         lr[k] = (uint32_t)popc(own & lanes_below(l));
     }
     __syncthreads();
-    if ((uint32_t)t < n_dest) {  // the units' exclusive prefixes, in array order
-        uint32_t run = 0;
-#pragma unroll
-        for (int u = 0; u < kArUnits; ++u) {
-            const uint32_t c = wc[u][t];
-            wc[u][t] = (uint16_t)run;
-            run += c;
-        }
-        tstart[t + 1] = run;  // the count for now
-    }
+    if ((uint32_t)t < n_dest) tstart[t + 1] = unit_prefix(wc, t);  // the count for now
     __syncthreads();
     if (t == 0) {
         uint32_t run = 0;
@@ -345,7 +320,6 @@ __global__ __launch_bounds__(kArBlock) void k_ar_emit(
     if (t < 4) reinterpret_cast<uint32_t*>(img + kArTile * FRAME)[t] = 0;
     __syncthreads();
     // every destination's run of the image to its place in that destination's output run
-    const uint32_t* img32 = reinterpret_cast<const uint32_t*>(img);
     for (uint32_t x = 0; x < n_dest; ++x) {
         const uint64_t g = first[(uint64_t)x * tiles + blockIdx.x];  // frames before the run
         const uint32_t s0 = tstart[x] * FRAME, bytes = (tstart[x + 1] - tstart[x]) * FRAME;
@@ -353,33 +327,8 @@ __global__ __launch_bounds__(kArBlock) void k_ar_emit(
         if (blockIdx.x == tiles - 1 && x == n_dest - 1 && t == 0)
             dest_off[n_dest] = g * FRAME + bytes;
         if (!bytes) continue;
-        uint8_t* d = out + g * FRAME;
-        // [0, head) bytewise up to the first 16-byte aligned address, then whole 16-byte
-        // chunks, then the tail bytewise
-        uint32_t head = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
-        head = head < bytes ? head : bytes;
-        const uint32_t nv = (bytes - head) / 16;
-        const uint32_t tail0 = head + nv * 16;
-        for (uint32_t i = t; i < nv; i += kArBlock) {
-            const uint32_t so = s0 + head + i * 16;  // image byte offset of the chunk
-            const uint32_t sh = so & 3u;
-            const uint32_t* q = img32 + (so >> 2);
-            const uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4];
-            uint4 v;
-            v.x = __builtin_amdgcn_alignbyte(a1, a0, sh);
-            v.y = __builtin_amdgcn_alignbyte(a2, a1, sh);
-            v.z = __builtin_amdgcn_alignbyte(a3, a2, sh);
-            v.w = __builtin_amdgcn_alignbyte(a4, a3, sh);
-            st_stream(reinterpret_cast<uint4*>(d + head) + i, v);
-        }
-        if ((uint32_t)t < head) d[t] = img[s0 + t];
-        if ((uint32_t)t >= 32u && (uint32_t)t - 32u < bytes - tail0)
-            d[tail0 + t - 32] = img[s0 + tail0 + t - 32];
+        copy_run_shifted(img, s0, bytes, out + g * FRAME, t);
     }
-}
-
-__global__ void k_ar_empty(uint64_t* dest_off, uint32_t n_dest) {
-    for (uint32_t x = threadIdx.x; x <= n_dest; x += blockDim.x) dest_off[x] = 0;
 }
 
 namespace {
@@ -404,7 +353,7 @@ hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replie
                                         uint64_t work_bytes, uint32_t* err, hipStream_t stream) {
     if (!n_dest || n_dest > (uint32_t)kArDest || n >= (1ull << 32)) return hipErrorInvalidValue;
     if (n == 0) {
-        k_ar_empty<<<1, 64, 0, stream>>>(dest_off, n_dest);
+        k_zero_u64<<<1, 64, 0, stream>>>(dest_off, n_dest + 1);
         return hipGetLastError();
     }
     Carver c(work);

@@ -3,7 +3,8 @@
 // as records. The two protocols share the handlers and the wire formats: no mode template.
 //
 // k_commit_handle: tile_walk (tile.hpp) hands every lane one instance and its messages in arrival
-// order, the skeleton of k_accept_handle; the lane applies
+// order, with the speculative state preload and the round counter of tile.hpp (TileState) that
+// k_accept_handle uses; the lane applies
 //   handleCommit       bareminpaxos.go:856-883 / paxos.go:522-549
 //   handleCommitShort  bareminpaxos.go:885-910 / paxos.go:551-575
 // to each with the instance in registers: a nil instance is installed COMMITTED at the message's
@@ -20,21 +21,24 @@
 // no touched flags, no memset), then the statuses from c + 1 in chunks of 64, one ballot and a
 // find-first per chunk.
 //
-// mpx_encode_commits: what bcastCommit -> SendMsg writes to every peer connection, the proposer
-// encoder's shape (proposer.hip):
+// mpx_encode_commits: what bcastCommit -> SendMsg writes to every peer connection, built from the
+// steps of frames.hpp that the proposer encoder uses (ring_pos, SizeIn / FrameOffOut, holder,
+// cmd_span, piece_scan / piece_item, image_or / image_or_cmd):
 //   1. k_ce_sizes, a thread per (destination q, send s): the frame's size (0 where q gets nothing)
 //   2. a destination-major scan of the sizes in place: frame_off[] and dest_off[]
 //   3. k_ce_emit: a workgroup per 8 KB output window deals out the pieces (a header, a command) of
 //      the frames that overlap it; the LDS image is laid out at the output's 16-byte phase, so the
-//      inside leaves as 16-byte stores whatever the output's address, the two ends bytewise.
+//      inside leaves as 16-byte stores whatever the output's address, the two ends bytewise
+//      (its own store-out: window_store of frames.hpp is the aligned-or-bytewise form).
 // Not thrifty, every frame is a 17-byte CommitShort and the call takes a send-major path of its
-// own (k_cs_count, a scan of the per-tile counts, k_cs_emit: the shape of the AcceptReply encoder),
-// which keeps no per-(destination, send) array.
+// own (k_cs_count, a scan of the per-tile counts, k_cs_emit: frames.hpp's partition steps, as in
+// the AcceptReply encoder), which keeps no per-(destination, send) array.
 //
 // mpx_gather_commit_shorts: one scan (scan.hpp) of the code-11 flags of mpx_decode_stream's
 // mpx_peer_frame list whose output step is the gather: the 16 body bytes at offset + 1 from the
 // two enclosing aligned vectors.
 #include "common.hpp"
+#include "frames.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
 #include "tile.hpp"
@@ -71,23 +75,15 @@ __global__ __launch_bounds__(kTileBlock) void k_commit_handle(
     const int4* m4 = reinterpret_cast<const int4*>(msgs);
     int4* s4 = reinterpret_cast<int4*>(st);
     int4* log4 = reinterpret_cast<int4*>(log_recs);
-    int64_t spec_idx = -1;  // the state loaded ahead for round 0 (tile_walk's pre)
-    int4 spec = make_int4(0, 0, 0, 0);
-    uint32_t round = 0;     // rounds of the current tile done by this thread
-    auto pre = [&](int32_t inst0) {
-        round = 0;
-        spec_idx = (int64_t)inst0 - base + t;
-        if (spec_idx >= 0 && (uint64_t)spec_idx < n_inst) spec = ld_stream(s4 + spec_idx);
-    };
+    TileState ts;
+    auto pre = [&](int32_t inst0) { ts.preload(s4, inst0, base, n_inst, t); };
     tile_walk(S, m4, n, err, pre, [&](uint32_t a, uint32_t cnt, uint64_t after, uint64_t oend,
                                       bool own, int64_t, bool) {
         const int32_t inst = own ? S.rec[a].x : 0;
         const int64_t idx = (int64_t)inst - base;
         const bool inwin = own && idx >= 0 && (uint64_t)idx < n_inst;
         ebits |= (own && !inwin) ? kErrNil : 0u;  // outside instanceSpace
-        int4 cur = inwin ? (idx == spec_idx ? spec : ld_stream(s4 + idx))
-                         : make_int4(MPX_STATUS_NIL, 0, 0, 0);
-        spec_idx = -1;  // (later rounds of the tile load their own)
+        int4 cur = ts.take(s4, inwin, idx);
         // the tile part: the durable-log record takes the message's place in the LDS tile
         for (uint32_t j = 0; j < cnt; ++j) {
             const int4 m = S.rec[a + j];
@@ -105,8 +101,7 @@ __global__ __launch_bounds__(kTileBlock) void k_commit_handle(
         }
         if (inwin) st_stream(s4 + idx, cur);
         // after the tile's last round: the tile's outputs [first head, end), coalesced
-        ++round;
-        if (round * kTileBlock < S.nh) return;  // (uniform: nh is the workgroup's)
+        if (!ts.last_round(S)) return;
         __syncthreads();
         const uint64_t p0 = ((after - 1) / kTileRecs) * kTileRecs;
         const uint32_t end = (uint32_t)(after - p0), h0 = S.hpos[0];
@@ -196,26 +191,13 @@ hipError_t launch_commit_handle(const mpx_accept_msg* msgs, uint64_t n, mpx_acce
 
 // ---- the Commit bytes -----------------------------------------------------------------------------
 namespace {
-constexpr int kCeBlock = 256;
+constexpr int kCeBlock = kFrBlock;
 constexpr int kCeWaves = kCeBlock / kWave;
 constexpr int kCeWindow = 8192;            // bytes of one output window
 constexpr int kCeImage = kCeWindow + 16;   // ... at the output's 16-byte phase
+constexpr int kCeWords = kCeImage / 4;
 constexpr int kCeGrid = 8192;              // workgroups at most (windows are walked grid-stride)
 constexpr uint32_t kCeNone = 0, kCeShort = 1, kCeFull = 2;
-
-__device__ __forceinline__ uint32_t ce_varint_len(uint64_t n) {  // binary.PutVarint of n >= 0
-    uint64_t u = n << 1;
-    uint32_t l = 1;
-    while (u >= 0x80) {
-        u >>= 7;
-        ++l;
-    }
-    return l;
-}
-__device__ __forceinline__ uint32_t ce_varint_byte(uint64_t n, uint32_t k) {
-    const uint64_t u = (n << 1) >> (7 * k);
-    return (uint32_t)(u & 0x7F) | (u >= 0x80 ? 0x80u : 0u);
-}
 
 // the device's view of a call
 struct CeArgs {
@@ -247,13 +229,10 @@ __device__ __forceinline__ uint32_t ce_kind(uint32_t q, uint32_t self, uint32_t 
                                             uint32_t alive) {
     if (q == self) return kCeNone;
     const uint32_t n1 = thrifty ? N >> 1 : N - 1;
-    const uint32_t p = (q + N - self - 1) % N;  // ring position: 0 = self + 1
-    // rot bit k = Alive[(self + 1 + k) % N]
-    const uint32_t full = N >= 32 ? ~0u : (1u << N) - 1u;
-    const uint32_t am = alive & full, sh = (self + 1) % N;
-    const uint32_t rot = sh ? ((am >> sh) | (am << (N - sh))) & full : am;
-    if (!((rot >> p) & 1u)) return kCeNone;
-    if ((uint32_t)__popc(rot & ((1u << p) - 1u)) < n1) return kCeShort;
+    uint32_t before;
+    ring_pos(q, self, N, alive, before);
+    if (before == kRingDead) return kCeNone;
+    if (before < n1) return kCeShort;
     return thrifty ? kCeFull : kCeNone;
 }
 
@@ -307,25 +286,24 @@ __device__ __forceinline__ CeFrame ce_frame(const CeArgs& a, uint64_t item, uint
     f.inst = x.inst;
     f.ballot = x.ballot;
     if (f.kind == kCeShort) f.bytes = MPX_COMMIT_SHORT_FRAME;
-    if (f.kind == kCeFull) f.bytes = 13ull + ce_varint_len(f.n) + 17ull * f.n;
+    if (f.kind == kCeFull) f.bytes = 13ull + varint_len(f.n) + 17ull * f.n;
     return f;
 }
 
 // ---- the not-thrifty case: every frame is a CommitShort ------------------------------------------
 // Every alive peer but the leader gets the 17 bytes, so the call is a stable partition of the
-// sends over the destinations fused with the encoding, the shape of mpx_encode_accept_replies
-// (acceptor.hip), with no per-(destination, send) array:
+// sends over the destinations fused with the encoding, on the partition steps of frames.hpp that
+// mpx_encode_accept_replies (acceptor.hip) uses, with no per-(destination, send) array:
 //   k_cs_count   a workgroup counts its tile's frames per destination into hist[dest][tile]
 //   exclusive scan of hist (scan.hpp): the first frame of every (destination, tile), and dest_off
 //   k_cs_emit    per destination, the tile ranks its sends (ballots: stable), encodes their frames
 //                into an LDS image and copies it to its place with 16-byte stores at 16-byte
 //                aligned addresses, the two ends bytewise, nothing at or past out_cap
-constexpr int kCsBlock = 256;
+constexpr int kCsBlock = kFrBlock;
 constexpr int kCsWaves = kCsBlock / kWave;
-constexpr int kCsPer = 4;                     // sends per lane per tile
-constexpr int kCsTile = kCsBlock * kCsPer;    // 1024 sends per tile
-constexpr int kCsUnits = kCsPer * kCsWaves;   // (register k, wave) units, in array order
-constexpr int kCsDest = MPX_MAX_REPLICAS;
+constexpr int kCsPer = kFrPer;                // sends per lane per tile
+constexpr int kCsTile = kFrTile;              // 1024 sends per tile
+constexpr int kCsDest = kFrDest;
 constexpr int kCsFrame = MPX_COMMIT_SHORT_FRAME;
 
 // bit q: q receives send x's CommitShort
@@ -349,44 +327,6 @@ struct CsFirstOut {
     }
 };
 
-// frame bytes of item (q, s), destination-major; k_ce_sizes leaves them in frame_off and the scan
-// runs in place (a tile reads its sizes before it writes its offsets)
-struct CeSizeIn {
-    const uint64_t* size;
-    __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return size[i]; }
-};
-struct CeFrameOut {
-    uint64_t* frame_off;
-    uint64_t* dest_off;
-    uint64_t n_sends, n_items;
-    __device__ __forceinline__ void operator()(uint64_t i, uint64_t s, uint64_t b) const {
-        frame_off[i] = s;
-        if (i % n_sends == 0) dest_off[i / n_sends] = s;
-        if (i == n_items - 1) {
-            frame_off[n_items] = s + b;
-            dest_off[n_items / n_sends] = s + b;
-        }
-    }
-};
-
-// OR the n bytes of w (little-endian dwords, bytes past n zero) into the zeroed image W at byte
-// offset s (may be negative; whatever falls outside the image is dropped)
-template <int ND>
-__device__ __forceinline__ void ce_or(uint32_t* W, int64_t s, const uint32_t (&w)[ND], uint32_t n) {
-    const int64_t d0 = s >> 2;
-    const uint32_t sh = (uint32_t)(s & 3) * 8u;
-    const uint32_t nout = (uint32_t)(((s & 3) + n + 3) >> 2);
-#pragma unroll
-    for (int i = 0; i <= ND; ++i) {
-        if ((uint32_t)i >= nout) break;
-        const int64_t d = d0 + i;
-        if (d < 0 || d >= kCeImage / 4) continue;
-        const uint64_t pair = ((uint64_t)(i < ND ? w[i] : 0u) << 32) | (i ? w[i - 1] : 0u);
-        const uint32_t v = (uint32_t)(pair >> (32 - sh));
-        if (v) atomicOr(&W[d], v);
-    }
-}
-
 // what a window needs of one frame, left in LDS by the item's thread for the piece threads
 struct CePiece {
     int64_t start;   // frame start - window start
@@ -402,10 +342,6 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_sizes(CeArgs a, uint64_t n_item
     const uint64_t i = (uint64_t)blockIdx.x * kCeBlock + threadIdx.x;
     if (i < n_items) size[i] = ce_frame(a, i, err).bytes;
 }
-__global__ void k_ce_empty(uint64_t* dest_off, uint32_t n_dest) {
-    for (uint32_t x = threadIdx.x; x <= n_dest; x += blockDim.x) dest_off[x] = 0;
-}
-
 __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* __restrict__ frame_off,
                                                       uint64_t n_items, uint8_t* __restrict__ out,
                                                       uint64_t out_cap) {
@@ -413,30 +349,16 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* 
     __shared__ uint32_t poff[kCeBlock + 1];
     __shared__ uint32_t wtot[kCeWaves];
     __shared__ __attribute__((aligned(16))) uint32_t W[kCeImage / 4];
-    const int t = threadIdx.x, l = lane_id(), w = t / kWave;
+    const int t = threadIdx.x;
     const uint64_t total = frame_off[n_items];
     const uint64_t lim = total < out_cap ? total : out_cap;  // nothing at or past out_cap
     const uint32_t ph = (uint32_t)((uintptr_t)out & 15u);    // image byte 0 is 16-byte aligned
-    // the item holding byte pos: the last i >= lo with frame_off[i] <= pos (256-ary search;
-    // invariant frame_off[lo] <= pos < frame_off[hi]). Every thread calls.
-    auto holder = [&](uint64_t lo, uint64_t pos) {
-        uint64_t hi = n_items;
-        while (hi - lo > 1) {
-            const uint64_t step = (hi - lo + kCeBlock - 1) / kCeBlock;
-            const uint64_t i = lo + (uint64_t)t * step;
-            const int c = __syncthreads_count(i < hi && frame_off[i] <= pos);
-            const uint64_t nh = lo + (uint64_t)c * step;
-            lo += (uint64_t)(c - 1) * step;
-            hi = nh < hi ? nh : hi;
-        }
-        return lo;
-    };
     for (uint64_t b0 = (uint64_t)blockIdx.x * kCeWindow; b0 < lim;
          b0 += (uint64_t)gridDim.x * kCeWindow) {
         const uint64_t b1 = b0 + kCeWindow < lim ? b0 + kCeWindow : lim;
         for (int i = t; i < kCeImage / 16; i += kCeBlock)
             reinterpret_cast<uint4*>(W)[i] = make_uint4(0, 0, 0, 0);
-        uint64_t c0 = holder(0, b0);
+        uint64_t c0 = holder(frame_off, n_items, 0, b0, t);
         for (;;) {
             const uint64_t i = c0 + t;
             uint32_t np = 0;
@@ -458,10 +380,9 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* 
                 p.cmd0 = 0;
                 uint32_t c_new = 0;
                 if (f.kind == kCeFull) {
-                    const uint64_t cs = fs + 13 + ce_varint_len(f.n);  // the Command slice
-                    const uint64_t jl = b0 > cs ? (b0 - cs) / 17 : 0;
-                    uint64_t jh = b1 > cs ? (b1 - cs + 16) / 17 : 0;
-                    jh = jh < f.n ? jh : f.n;
+                    const uint64_t cs = fs + 13 + varint_len(f.n);  // the Command slice
+                    const CmdSpan sp = cmd_span(cs, b0, b1);
+                    const uint64_t jl = sp.lo, jh = sp.hi < f.n ? sp.hi : f.n;
                     p.j0 = (uint32_t)jl;
                     p.cmd0 = f.first_cmd + jl;
                     c_new = jh > jl ? (uint32_t)(jh - jl) : 0u;
@@ -469,22 +390,9 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* 
                 fi[t] = p;
                 np = 1u + c_new;
             }
-            // exclusive scan of the piece counts over the workgroup
-            const uint32_t inc = wave_incl_scan(np, ScanSum32{});
-            if (l == kWave - 1) wtot[w] = inc;
-            __syncthreads();
-            uint32_t before = 0;
-            for (int x = 0; x < w; ++x) before += wtot[x];
-            poff[t] = before + inc - np;
-            if (t == kCeBlock - 1) poff[kCeBlock] = before + inc;
-            __syncthreads();
-            const uint32_t pieces = poff[kCeBlock];
+            const uint32_t pieces = piece_scan(np, poff, wtot, t);
             for (uint32_t p = t; p < pieces; p += kCeBlock) {
-                uint32_t fa = 0, fb = kCeBlock;  // the last item with poff <= p
-                while (fb - fa > 1) {
-                    const uint32_t mid = (fa + fb) >> 1;
-                    if (poff[mid] <= p) fa = mid; else fb = mid;
-                }
+                const uint32_t fa = piece_item(poff, p);
                 const CePiece& F = fi[fa];
                 const uint32_t k = p - poff[fa];
                 const uint32_t ld = (uint32_t)F.leader, in = (uint32_t)F.inst;
@@ -493,24 +401,21 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* 
                 if (k == 0 && F.kind == kCeShort) {  // [11][LeaderId][Instance][Count][Ballot]
                     const uint32_t h[5] = {MPX_PEER_COMMIT_SHORT | (ld << 8), (ld >> 24) | (in << 8),
                                            (in >> 24) | (F.n << 8), (F.n >> 24) | (bl << 8), bl >> 24};
-                    ce_or(W, at, h, MPX_COMMIT_SHORT_FRAME);
+                    image_or<kCeWords>(W, at, h, MPX_COMMIT_SHORT_FRAME);
                 } else if (k == 0) {  // [10][LeaderId][Instance][Ballot][V(n)]
-                    const uint32_t vn = ce_varint_len(F.n);
+                    const uint32_t vn = varint_len(F.n);
                     uint32_t h[5] = {MPX_PEER_COMMIT | (ld << 8), (ld >> 24) | (in << 8),
                                      (in >> 24) | (bl << 8), bl >> 24, 0u};
                     for (uint32_t x = 0; x < vn; ++x) {
                         const uint32_t b = 13 + x;
-                        h[b >> 2] |= ce_varint_byte(F.n, x) << (8 * (b & 3));
+                        h[b >> 2] |= varint_byte(F.n, x) << (8 * (b & 3));
                     }
-                    ce_or(W, at, h, 13 + vn);
+                    image_or<kCeWords>(W, at, h, 13 + vn);
                 } else {  // a command: Op u8, K i64, V i64
                     const uint64_t j = F.cmd0 + (k - 1);
                     const uint64_t k8 = (uint64_t)a.key[j], v8 = (uint64_t)a.val[j];
-                    const uint32_t kl = (uint32_t)k8, kh = (uint32_t)(k8 >> 32);
-                    const uint32_t vl = (uint32_t)v8, vh = (uint32_t)(v8 >> 32);
-                    const uint32_t c[5] = {(uint32_t)a.op[j] | (kl << 8), (kl >> 24) | (kh << 8),
-                                           (kh >> 24) | (vl << 8), (vl >> 24) | (vh << 8), vh >> 24};
-                    ce_or(W, at + 13 + ce_varint_len(F.n) + 17ll * (F.j0 + (k - 1)), c, 17);
+                    image_or_cmd<kCeWords>(W, at + 13 + varint_len(F.n) + 17ll * (F.j0 + (k - 1)),
+                                           a.op[j], k8, v8);
                 }
             }
             const uint64_t nx = c0 + kCeBlock;
@@ -518,7 +423,7 @@ __global__ __launch_bounds__(kCeBlock) void k_ce_emit(CeArgs a, const uint64_t* 
             __syncthreads();  // fi and poff are rewritten by the next chunk
             // a chunk without a byte (a destination that receives nothing is n_sends such items
             // in a row): on to the item that holds the next byte
-            c0 = pieces ? nx : holder(nx, frame_off[nx]);
+            c0 = pieces ? nx : holder(frame_off, n_items, nx, frame_off[nx], t);
         }
         __syncthreads();
         // image bytes [lo, hi) go to out + b0 - ph + [lo, hi): whole aligned vectors inside
@@ -539,21 +444,14 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_count(CeArgs a, uint64_t tiles,
                                                        uint32_t* __restrict__ hist, uint32_t* err) {
     __shared__ uint32_t cnt[kCsDest];
     const int t = threadIdx.x, l = lane_id();
-    if (t < kCsDest) cnt[t] = 0;
-    __syncthreads();
+    dest_count_begin(cnt, t);
     const uint64_t p0 = (uint64_t)blockIdx.x * kCsTile;
     uint32_t mine = 0;  // lane q < N: frames of the wave to destination q
 #pragma unroll
-    for (int k = 0; k < kCsPer; ++k) {
-        const uint32_t m = cs_mask(a, ce_send(a, p0 + k * kCsBlock + t, err));
-        for (uint32_t q = 0; q < a.nrep; ++q) {
-            const uint32_t c = (uint32_t)popc(ballot((m >> q) & 1u));
-            mine += (uint32_t)l == q ? c : 0u;
-        }
-    }
-    if ((uint32_t)l < a.nrep && mine) atomicAdd(&cnt[l], mine);
-    __syncthreads();
-    if ((uint32_t)t < a.nrep) hist[(uint64_t)t * tiles + blockIdx.x] = cnt[t];
+    for (int k = 0; k < kCsPer; ++k)
+        mine = dest_count_wave<kDestMask>(
+            mine, cs_mask(a, ce_send(a, p0 + k * kCsBlock + t, err)), a.nrep, l);
+    dest_count_end(cnt, mine, a.nrep, tiles, hist, t, l);
 }
 
 __global__ __launch_bounds__(kCsBlock) void k_cs_emit(CeArgs a, uint64_t tiles,
@@ -561,7 +459,7 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_emit(CeArgs a, uint64_t tiles,
                                                       uint8_t* __restrict__ out, uint64_t out_cap) {
     // one destination's frames of the tile; 16 spare bytes for the last chunk's shifted reads
     __shared__ __attribute__((aligned(16))) uint8_t img[kCsTile * kCsFrame + 16];
-    __shared__ uint16_t wc[kCsUnits][kCsDest];  // per (k, wave) unit: count, then exclusive prefix
+    __shared__ uint16_t wc[kFrUnits][kCsDest];  // per (k, wave) unit: count, then exclusive prefix
     __shared__ uint32_t tot[kCsDest];           // the tile's frames per destination
     const int t = threadIdx.x, l = lane_id(), w = t / kWave;
     const uint64_t p0 = (uint64_t)blockIdx.x * kCsTile;
@@ -571,29 +469,16 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_emit(CeArgs a, uint64_t tiles,
     for (int k = 0; k < kCsPer; ++k) {
         x[k] = ce_send(a, p0 + k * kCsBlock + t, nullptr);  // (k_cs_count raised the errors)
         m[k] = cs_mask(a, x[k]);
-        for (uint32_t q = 0; q < a.nrep; ++q) {
-            const uint64_t mq = ballot((m[k] >> q) & 1u);
-            if ((uint32_t)l == q) wc[k * kCsWaves + w][q] = (uint16_t)popc(mq);
-        }
+        unit_count<kDestMask>(wc[k * kCsWaves + w], m[k], a.nrep, l);
     }
     __syncthreads();
-    if ((uint32_t)t < a.nrep) {  // the units' exclusive prefixes, in array order
-        uint32_t run = 0;
-#pragma unroll
-        for (int u = 0; u < kCsUnits; ++u) {
-            const uint32_t c = wc[u][t];
-            wc[u][t] = (uint16_t)run;
-            run += c;
-        }
-        tot[t] = run;
-    }
+    if ((uint32_t)t < a.nrep) tot[t] = unit_prefix(wc, t);
     if (t < 4) reinterpret_cast<uint32_t*>(img + kCsTile * kCsFrame)[t] = 0;
     __syncthreads();
-    const uint32_t* img32 = reinterpret_cast<const uint32_t*>(img);
     for (uint32_t q = 0; q < a.nrep; ++q) {
 #pragma unroll
         for (int k = 0; k < kCsPer; ++k) {
-            const bool on = (m[k] >> q) & 1u;
+            const bool on = dest_is<kDestMask>(m[k], q);
             const uint64_t mq = ballot(on);
             if (!on) continue;
             const uint32_t pos = wc[k * kCsWaves + w][q] + (uint32_t)popc(mq & lanes_below(l));
@@ -608,30 +493,7 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_emit(CeArgs a, uint64_t tiles,
         const uint64_t start = first[(uint64_t)q * tiles + blockIdx.x] * kCsFrame;
         uint32_t bytes = tot[q] * kCsFrame;
         if (start < out_cap && out_cap - start < bytes) bytes = (uint32_t)(out_cap - start);
-        if (bytes && start < out_cap) {
-            uint8_t* d = out + start;
-            // [0, head) bytewise up to the first 16-byte aligned address, then whole 16-byte
-            // chunks, then the tail bytewise
-            uint32_t head = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
-            head = head < bytes ? head : bytes;
-            const uint32_t nv = (bytes - head) / 16;
-            const uint32_t tail0 = head + nv * 16;
-            for (uint32_t i = t; i < nv; i += kCsBlock) {
-                const uint32_t so = head + i * 16;  // image byte offset of the chunk
-                const uint32_t sh = so & 3u;
-                const uint32_t* s = img32 + (so >> 2);
-                const uint32_t a0 = s[0], a1 = s[1], a2 = s[2], a3 = s[3], a4 = s[4];
-                uint4 v;
-                v.x = __builtin_amdgcn_alignbyte(a1, a0, sh);
-                v.y = __builtin_amdgcn_alignbyte(a2, a1, sh);
-                v.z = __builtin_amdgcn_alignbyte(a3, a2, sh);
-                v.w = __builtin_amdgcn_alignbyte(a4, a3, sh);
-                st_stream(reinterpret_cast<uint4*>(d + head) + i, v);
-            }
-            if ((uint32_t)t < head) d[t] = img[t];
-            if ((uint32_t)t >= 32u && (uint32_t)t - 32u < bytes - tail0)
-                d[tail0 + t - 32] = img[tail0 + t - 32];
-        }
+        if (bytes && start < out_cap) copy_run_shifted(img, 0, bytes, out + start, t);
         __syncthreads();  // the next destination rewrites the image
     }
 }
@@ -705,8 +567,6 @@ struct CmWork {
 };
 }  // namespace
 
-__global__ void k_gs_zero(uint64_t* n_shorts) { *n_shorts = 0; }
-
 uint64_t commits_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_other, Carver&& c) {
     return CmWork(c, nrep, n_sends, n_other), c.bytes();
 }
@@ -719,7 +579,7 @@ hipError_t launch_encode_commits(int32_t nrep, const mpx_commit_batch* b, uint8_
     const uint64_t items = (uint64_t)nrep * b->n_sends;
     if (b->n_sends >= (1ull << 32) || n_inst > (1ull << 32)) return hipErrorInvalidValue;
     if (items == 0) {
-        k_ce_empty<<<1, 64, 0, stream>>>(dest_off, (uint32_t)nrep);
+        k_zero_u64<<<1, 64, 0, stream>>>(dest_off, (uint32_t)nrep + 1);
         return hipGetLastError();
     }
     Carver c(work);
@@ -752,8 +612,8 @@ hipError_t launch_encode_commits(int32_t nrep, const mpx_commit_batch* b, uint8_
     }
     k_ce_sizes<<<(unsigned)((items + kCeBlock - 1) / kCeBlock), kCeBlock, 0, stream>>>(
         a, items, w.frame_off, err);
-    const hipError_t r = device_scan(CeSizeIn{w.frame_off},
-                                     CeFrameOut{w.frame_off, dest_off, a.n_sends, items}, items,
+    const hipError_t r = device_scan(SizeIn{w.frame_off},
+                                     FrameOffOut{w.frame_off, dest_off, a.n_sends, items}, items,
                                      ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
     if (r != hipSuccess) return r;
     const uint64_t windows = (out_cap + kCeWindow - 1) / kCeWindow;
@@ -770,7 +630,7 @@ hipError_t launch_gather_commit_shorts(const uint8_t* buf, uint64_t len, const m
                                        uint64_t work_bytes, uint32_t* err, hipStream_t stream) {
     if (n_other >= (1ull << 32) || len > MPX_DECODE_MAX_BYTES) return hipErrorInvalidValue;
     if (!n_other) {
-        k_gs_zero<<<1, 1, 0, stream>>>(n_shorts);
+        k_zero_u64<<<1, 1, 0, stream>>>(n_shorts, 1);
         return hipGetLastError();
     }
     Carver c(work);

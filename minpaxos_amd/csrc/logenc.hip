@@ -16,16 +16,19 @@
 // per block, the overlapping records' headers and commands are written into an LDS image of the
 // block (one thread per header, one per command, so the command loads are coalesced) and the
 // image goes out as 16-byte vector stores (no partial lines except at the run's two ends).
+// The byte-level pieces are frames.hpp's, shared with the Phase-2 encoders: the varint pair,
+// image_or / image_or_cmd, cmd_span, window_store, k_zero_u64.
 #include <cstring>
 
 #include "common.hpp"
+#include "frames.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
 
 namespace mpx {
 
 namespace {
-constexpr int kLogBlock = 256;
+constexpr int kLogBlock = kFrBlock;
 // output window of one emit block: kLogWindowVec 16-byte vectors per thread (8 KB: 4 KB
 // windows measured 14% slower, 16 KB ones 13% slower at 3 workgroups per CU)
 constexpr int kLogWindowVec = 2;
@@ -36,20 +39,10 @@ constexpr int kLogMaxRecs = kLogBlockBytes / kLogMinRec + 2;
 // commands overlapping one window: at most a whole 17 bytes each, plus a partial one per end
 constexpr int kLogMaxCmds = kLogBlockBytes / 17 + 3;
 
-__host__ __device__ __forceinline__ uint64_t zigzag(int64_t x) {  // binary.PutVarint's mapping
+// binary.PutVarint's mapping, in full: with the n >= 0 form of frames.hpp (varint_len) the compiler
+// cannot know a record's command count non-negative, and the device code changes
+__host__ __device__ __forceinline__ uint64_t zigzag(int64_t x) {
     return x < 0 ? ~((uint64_t)x << 1) : (uint64_t)x << 1;
-}
-__host__ __device__ __forceinline__ uint32_t uvarint_len(uint64_t u) {
-    uint32_t l = 1;
-    while (u >= 0x80) {
-        u >>= 7;
-        ++l;
-    }
-    return l;
-}
-__device__ __forceinline__ uint32_t uvarint_byte(uint64_t u, uint32_t k) {
-    u >>= 7 * k;
-    return (uint32_t)(u & 0x7F) | (u >= 0x80 ? 0x80u : 0u);
 }
 __host__ __device__ __forceinline__ uint32_t hdr_bytes(int format, uint64_t ncmd) {
     return format == MPX_LOG_CATCHUP ? 8u + uvarint_len(zigzag((int64_t)ncmd)) : 12u;
@@ -81,29 +74,6 @@ struct RecOffOut {
             blk_first[b] = i;
     }
 };
-
-__global__ void k_log_zero(uint64_t* rec_off) { rec_off[0] = 0; }
-
-// OR the n bytes of w (little-endian dwords, bytes past n zero) into the zeroed LDS window W at
-// byte offset s (may be negative: the part before the window is dropped, as is anything past
-// it): one ds_or_b32 per touched dword, so two writers of one dword (a record boundary inside
-// it) meet in the OR
-template <int ND>
-__device__ __forceinline__ void or_bytes(uint32_t* W, int64_t s, const uint32_t (&w)[ND],
-                                         uint32_t n) {
-    const int64_t d0 = s >> 2;  // floor
-    const uint32_t sh = (uint32_t)(s & 3) * 8u;
-    const uint32_t nout = (uint32_t)(((s & 3) + n + 3) >> 2);
-#pragma unroll
-    for (int i = 0; i <= ND; ++i) {
-        if ((uint32_t)i >= nout) break;
-        const int64_t d = d0 + i;
-        if (d < 0 || d >= kLogBlockBytes / 4) continue;
-        const uint64_t pair = ((uint64_t)(i < ND ? w[i] : 0u) << 32) | (i ? w[i - 1] : 0u);
-        const uint32_t v = (uint32_t)(pair >> (32 - sh));
-        if (v) atomicOr(&W[d], v);
-    }
-}
 
 // rec_off: n+1 record offsets (rec_off[n] = total bytes). One block per 8 KB output window:
 // the records overlapping it are first .. first+nr-1 (blk_first of this block and the next).
@@ -142,11 +112,11 @@ __global__ __launch_bounds__(kLogBlock) void k_log_emit(
     {
         const uint64_t hb0 = off[1] - off[0] - 17 * (coff[1] - coff[0]);
         const uint64_t cs0 = off[0] + hb0;  // first record's commands start here
-        j_lo = coff[0] + (b0 > cs0 ? (b0 - cs0) / 17 : 0);
+        j_lo = coff[0] + cmd_span(cs0, b0, b1).lo;
         const uint64_t L = nr - 1;
         const uint64_t hbl = off[L + 1] - off[L] - 17 * (coff[L + 1] - coff[L]);
         const uint64_t csl = off[L] + hbl;
-        const uint64_t c = b1 > csl ? (b1 - csl + 16) / 17 : 0;
+        const uint64_t c = cmd_span(csl, b0, b1).hi;
         j_hi = coff[L] + c < coff[L + 1] ? coff[L] + c : coff[L + 1];
     }
     // headers, and the command -> record map
@@ -164,7 +134,7 @@ __global__ __launch_bounds__(kLogBlock) void k_log_emit(
             const uint64_t zz = zigzag((int64_t)nc);
             for (uint32_t q = 0; q + 8 < hb; ++q) h[2 + (q >> 2)] |= uvarint_byte(zz, q) << (8 * (q & 3));
         }
-        or_bytes(W, (int64_t)(rs - b0), h, hb);
+        image_or<kLogBlockBytes / 4>(W, (int64_t)(rs - b0), h, hb);
     }
     __syncthreads();
     for (uint64_t j = j_lo + threadIdx.x; j < j_hi; j += kLogBlock) {
@@ -172,26 +142,11 @@ __global__ __launch_bounds__(kLogBlock) void k_log_emit(
         const uint64_t nc = coff[lo + 1] - coff[lo];
         const uint64_t cs = off[lo + 1] - 17 * nc;  // commands of record lo start here
         const uint64_t pos = cs + 17 * (j - coff[lo]);
-        const uint32_t o8 = op[j];
-        const uint64_t k8 = (uint64_t)key[j], v8 = (uint64_t)val[j];
-        const uint32_t kl = (uint32_t)k8, kh = (uint32_t)(k8 >> 32);
-        const uint32_t vl = (uint32_t)v8, vh = (uint32_t)(v8 >> 32);
-        const uint32_t c[5] = {o8 | (kl << 8), (kl >> 24) | (kh << 8), (kh >> 24) | (vl << 8),
-                               (vl >> 24) | (vh << 8), vh >> 24};
-        or_bytes(W, (int64_t)pos - (int64_t)b0, c, 17);
+        image_or_cmd<kLogBlockBytes / 4>(W, (int64_t)pos - (int64_t)b0, op[j], (uint64_t)key[j],
+                                         (uint64_t)val[j]);
     }
     __syncthreads();
-    const uint32_t bytes = (uint32_t)(b1 - b0);
-    const uint8_t* S = reinterpret_cast<const uint8_t*>(W);
-    uint8_t* dst = out + b0;
-    if (((uintptr_t)dst & 15) == 0) {
-        const uint32_t nv = bytes / 16;
-        for (uint32_t i = threadIdx.x; i < nv; i += kLogBlock)
-            st_stream(reinterpret_cast<uint4*>(dst) + i, reinterpret_cast<const uint4*>(W)[i]);
-        for (uint32_t i = nv * 16 + threadIdx.x; i < bytes; i += kLogBlock) dst[i] = S[i];
-    } else {
-        for (uint32_t i = threadIdx.x; i < bytes; i += kLogBlock) dst[i] = S[i];
-    }
+    window_store(W, (uint32_t)(b1 - b0), out + b0, (int)threadIdx.x);
 }
 
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m) { return n * (8 + 10) + 17 * m; }
@@ -223,7 +178,7 @@ hipError_t launch_encode_log(int format, const mpx_log_rec* recs, uint64_t n,
     Carver c(work);
     const LogWork w(c, n, m);
     if (work_bytes < c.bytes()) return hipErrorInvalidValue;
-    k_log_zero<<<1, 1, 0, stream>>>(rec_off);
+    k_zero_u64<<<1, 1, 0, stream>>>(rec_off, 1);
     if (n == 0) return hipGetLastError();
     const uint64_t blocks = blocks_for(n, m);
     const hipError_t r = device_scan(RecBytes{format, cmd_off},

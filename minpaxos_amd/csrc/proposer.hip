@@ -21,7 +21,8 @@
 //   CLASSIC  paxosprotomarsh.go:214-242     LeaderId, Instance, Ballot, V(n), n Commands
 // Nothing is materialised per frame or per group:
 //   1. a scan (scan.hpp) of the window's log records' encoded sizes: log_off[], so a catch-up
-//      range's bytes are a difference of two prefix sums (the RecBytes idea of logenc.hip)
+//      range's bytes are a difference of two prefix sums (sizes computed from cmd_off by the
+//      scan's input functor, as in logenc.hip)
 //   2. k_ab_sizes, a thread per (destination q, send s): the frame's size (0 where q is not a
 //      destination of s or the slot is skipped), and a destination-major scan of the sizes in
 //      place: frame_off[] and dest_off[]
@@ -32,7 +33,11 @@
 //      the threads, whatever the mix (one 85 KB frame over many windows, or a hundred small
 //      frames in one); each piece is ORed into the LDS image as dwords and the image leaves as
 //      16-byte stores.
+// The steps are frames.hpp's, shared with commit.hip and logenc.hip: varint_len/_byte, ring_pos,
+// SizeIn / FrameOffOut, holder, cmd_span, piece_scan / piece_item, image_or / image_or_cmd,
+// window_store, k_zero_u64. Here: the handler, the frame layout (ab_frame, AbPiece), the loop.
 #include "common.hpp"
+#include "frames.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
 
@@ -132,25 +137,12 @@ hipError_t launch_propose_handle(int mode, mpx_proposer_group* groups, uint64_t 
 
 // ---- the Accept bytes ----------------------------------------------------------------------------
 namespace {
-constexpr int kAbBlock = 256;
+constexpr int kAbBlock = kFrBlock;
 constexpr int kAbWaves = kAbBlock / kWave;
 constexpr int kAbWindowVec = 2;  // 16-byte vectors per thread in one output window
 constexpr int kAbWindow = kAbBlock * 16 * kAbWindowVec;  // bytes of one output window
+constexpr int kAbWords = kAbWindow / 4;               // ... as the dwords of its LDS image
 constexpr int kAbGrid = 8192;             // workgroups at most (windows are walked grid-stride)
-
-__device__ __forceinline__ uint32_t ab_varint_len(uint64_t n) {  // binary.PutVarint of n >= 0
-    uint64_t u = n << 1;
-    uint32_t l = 1;
-    while (u >= 0x80) {
-        u >>= 7;
-        ++l;
-    }
-    return l;
-}
-__device__ __forceinline__ uint32_t ab_varint_byte(uint64_t n, uint32_t k) {
-    const uint64_t u = (n << 1) >> (7 * k);
-    return (uint32_t)(u & 0x7F) | (u >= 0x80 ? 0x80u : 0u);
-}
 
 // the device's view of a call
 struct AbArgs {
@@ -188,14 +180,10 @@ __device__ __forceinline__ bool ab_is_dest(uint32_t q, uint32_t self, uint32_t N
                                            uint32_t alive) {
     if (q == self) return false;
     const uint32_t want = thrifty ? N >> 1 : N - 1;
-    const uint32_t p = (q + N - self - 1) % N;  // ring position: 0 = self + 1
+    uint32_t before;
+    const uint32_t p = ring_pos(q, self, N, alive, before);
     if (MODE == MPX_MODE_MIN) return p < want;  // a dead peer is reconnected and counted (:476-482)
-    // CLASSIC (:323-327): dead peers are passed over; rot bit k = Alive[(self + 1 + k) % N]
-    const uint32_t full = N >= 32 ? ~0u : (1u << N) - 1u;
-    const uint32_t am = alive & full, sh = (self + 1) % N;
-    const uint32_t rot = sh ? ((am >> sh) | (am << (N - sh))) & full : am;
-    if (!((rot >> p) & 1u)) return false;
-    return (uint32_t)__popc(rot & ((1u << p) - 1u)) < want;
+    return before != kRingDead && before < want;  // CLASSIC (:323-327): dead peers are passed over
 }
 
 template <int MODE>
@@ -227,7 +215,7 @@ __device__ __forceinline__ AbFrame ab_frame(const AbArgs& a, uint64_t item, uint
     f.lc = s0.z;
     f.lo = 0;
     f.L0 = 0;
-    const uint32_t vn = ab_varint_len(f.n);
+    const uint32_t vn = varint_len(f.n);
     if (MODE != MPX_MODE_MIN) {
         f.bytes = 13ull + vn + 17ull * f.n;
         return f;
@@ -246,7 +234,7 @@ __device__ __forceinline__ AbFrame ab_frame(const AbArgs& a, uint64_t item, uint
         f.L0 = a.log_off[lo];
         logb = a.log_off[lc + 1] - f.L0;
     }
-    f.bytes = 17ull + vn + 17ull * f.n + ab_varint_len(f.m) + logb;
+    f.bytes = 17ull + vn + 17ull * f.n + varint_len(f.m) + logb;
     return f;
 }
 
@@ -255,7 +243,7 @@ struct AbRecBytes {
     const uint64_t* coff;
     __device__ __forceinline__ uint64_t operator()(uint64_t i) const {
         const uint64_t nc = coff[i + 1] - coff[i];
-        return 8u + ab_varint_len(nc) + 17 * nc;
+        return 8u + varint_len(nc) + 17 * nc;
     }
 };
 struct AbRecOut {
@@ -264,54 +252,9 @@ struct AbRecOut {
         log_off[i + 1] = s + b;
     }
 };
-// scan 2: frame bytes of item (q, s), destination-major. k_ab_sizes leaves them in frame_off (a
-// thread per item: the chain send -> group -> peer commit -> log_off runs in every lane at once;
-// as the scan's own input functor it ran 16 dependent rounds per lane in 80 workgroups, 56 us
-// for 327,680 items), and the scan runs in place: a tile reads its sizes before it writes its
-// offsets, and no tile reads another's.
-struct AbSizeIn {
-    const uint64_t* size;
-    __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return size[i]; }
-};
-struct AbFrameOut {
-    uint64_t* frame_off;
-    uint64_t* dest_off;
-    uint64_t n_sends, n_items;
-    __device__ __forceinline__ void operator()(uint64_t i, uint64_t s, uint64_t b) const {
-        frame_off[i] = s;
-        if (i % n_sends == 0) dest_off[i / n_sends] = s;
-        if (i == n_items - 1) {
-            frame_off[n_items] = s + b;
-            dest_off[n_items / n_sends] = s + b;
-        }
-    }
-};
-
-// OR the n bytes of w (little-endian dwords, bytes past n zero) into the zeroed window W at byte
-// offset s (may be negative; whatever falls outside the window is dropped)
-template <int ND>
-__device__ __forceinline__ void ab_or(uint32_t* W, int64_t s, const uint32_t (&w)[ND], uint32_t n) {
-    const int64_t d0 = s >> 2;
-    const uint32_t sh = (uint32_t)(s & 3) * 8u;
-    const uint32_t nout = (uint32_t)(((s & 3) + n + 3) >> 2);
-#pragma unroll
-    for (int i = 0; i <= ND; ++i) {
-        if ((uint32_t)i >= nout) break;
-        const int64_t d = d0 + i;
-        if (d < 0 || d >= kAbWindow / 4) continue;
-        const uint64_t pair = ((uint64_t)(i < ND ? w[i] : 0u) << 32) | (i ? w[i - 1] : 0u);
-        const uint32_t v = (uint32_t)(pair >> (32 - sh));
-        if (v) atomicOr(&W[d], v);
-    }
-}
-__device__ __forceinline__ void ab_or_cmd(uint32_t* W, int64_t s, uint32_t o8, uint64_t k8,
-                                          uint64_t v8) {
-    const uint32_t kl = (uint32_t)k8, kh = (uint32_t)(k8 >> 32);
-    const uint32_t vl = (uint32_t)v8, vh = (uint32_t)(v8 >> 32);
-    const uint32_t c[5] = {o8 | (kl << 8), (kl >> 24) | (kh << 8), (kh >> 24) | (vl << 8),
-                           (vl >> 24) | (vh << 8), vh >> 24};
-    ab_or(W, s, c, 17);
-}
+// scan 2: frame bytes of item (q, s), destination-major: k_ab_sizes leaves them in frame_off (the
+// chain send -> group -> peer commit -> log_off runs in every lane at once; as the scan's input
+// functor it took 56 us for 327,680 items), scanned in place by SizeIn / FrameOffOut (frames.hpp)
 
 // what a window needs of one frame, left in LDS by the item's thread for the piece threads
 struct AbPiece {
@@ -327,18 +270,12 @@ struct AbPiece {
 };
 }  // namespace
 
-__global__ void k_ab_zero(uint64_t* p) { p[0] = 0; }
-
 template <int MODE>
 __global__ __launch_bounds__(kAbBlock) void k_ab_sizes(AbArgs a, uint64_t n_items,
                                                        uint64_t* __restrict__ size, uint32_t* err) {
     const uint64_t i = (uint64_t)blockIdx.x * kAbBlock + threadIdx.x;
     if (i < n_items) size[i] = ab_frame<MODE>(a, i, err).bytes;
 }
-__global__ void k_ab_empty(uint64_t* dest_off, uint32_t n_dest) {
-    for (uint32_t x = threadIdx.x; x <= n_dest; x += blockDim.x) dest_off[x] = 0;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* __restrict__ frame_off,
                                                       uint64_t n_items, uint8_t* __restrict__ out,
@@ -348,7 +285,7 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
     __shared__ uint32_t wtot[kAbWaves];
     __shared__ __attribute__((aligned(16))) uint32_t W[kAbWindow / 4];
     constexpr uint32_t kHead = MODE == MPX_MODE_MIN ? 17u : 13u;
-    const int t = threadIdx.x, l = lane_id(), w = t / kWave;
+    const int t = threadIdx.x;
     const uint64_t total = frame_off[n_items];
     const uint64_t lim = total < out_cap ? total : out_cap;  // nothing at or past out_cap
     for (uint64_t b0 = (uint64_t)blockIdx.x * kAbWindow; b0 < lim;
@@ -357,17 +294,7 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
 #pragma unroll
         for (int v = 0; v < kAbWindowVec; ++v)
             reinterpret_cast<uint4*>(W)[t + v * kAbBlock] = make_uint4(0, 0, 0, 0);
-        // the item holding byte b0: the last i with frame_off[i] <= b0 (256-ary search; invariant
-        // frame_off[lo] <= b0 < frame_off[hi])
-        uint64_t lo = 0, hi = n_items;
-        while (hi - lo > 1) {
-            const uint64_t step = (hi - lo + kAbBlock - 1) / kAbBlock;
-            const uint64_t i = lo + (uint64_t)t * step;
-            const int c = __syncthreads_count(i < hi && frame_off[i] <= b0);
-            const uint64_t nh = lo + (uint64_t)c * step;
-            lo += (uint64_t)(c - 1) * step;
-            hi = nh < hi ? nh : hi;
-        }
+        const uint64_t lo = holder(frame_off, n_items, 0, b0, t);  // the item holding byte b0
         for (uint64_t c0 = lo;; c0 += kAbBlock) {
             const uint64_t i = c0 + t;
             uint32_t np = 0;
@@ -387,10 +314,9 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                 p.ballot = f.ballot;
                 p.lc = f.lc;
                 p.L0 = f.L0;
-                const uint64_t cs = fs + kHead + ab_varint_len(f.n);  // the Command slice
-                const uint64_t jl = b0 > cs ? (b0 - cs) / 17 : 0;
-                uint64_t jh = b1 > cs ? (b1 - cs + 16) / 17 : 0;
-                jh = jh < f.n ? jh : f.n;
+                const uint64_t cs = fs + kHead + varint_len(f.n);  // the Command slice
+                const CmdSpan sp = cmd_span(cs, b0, b1);
+                const uint64_t jl = sp.lo, jh = sp.hi < f.n ? sp.hi : f.n;
                 p.j0 = (uint32_t)jl;
                 p.cmd0 = f.first_cmd + jl;
                 p.c_new = jh > jl ? (uint32_t)(jh - jl) : 0u;
@@ -399,7 +325,7 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                 p.lcmd0 = 0;
                 if (MODE == MPX_MODE_MIN && f.m) {
                     // the window in the log's byte coordinates: [x0, x1) of [L0, L1)
-                    const uint64_t ls = cs + 17ull * f.n + ab_varint_len(f.m);
+                    const uint64_t ls = cs + 17ull * f.n + varint_len(f.m);
                     const uint64_t L1 = f.L0 + (fe - ls);
                     const uint64_t x0 = b0 > ls ? f.L0 + (b0 - ls) : f.L0;
                     const uint64_t x1 = b1 > ls ? (f.L0 + (b1 - ls) < L1 ? f.L0 + (b1 - ls) : L1)
@@ -424,8 +350,8 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                         const uint64_t cb0 = a.lcoff[i1], cb1 = a.lcoff[i1 + 1];
                         const uint64_t cs0 = a.log_off[i0 + 1] - 17 * (ca1 - ca0);
                         const uint64_t cs1 = a.log_off[i1 + 1] - 17 * (cb1 - cb0);
-                        const uint64_t la = ca0 + (x0 > cs0 ? (x0 - cs0) / 17 : 0);
-                        uint64_t lh = cb0 + (x1 > cs1 ? (x1 - cs1 + 16) / 17 : 0);
+                        const uint64_t la = ca0 + cmd_span(cs0, x0, x1).lo;
+                        uint64_t lh = cb0 + cmd_span(cs1, x0, x1).hi;
                         lh = lh < cb1 ? lh : cb1;
                         p.lcmd0 = la;
                         p.c_log = lh > la ? (uint32_t)(lh - la) : 0u;
@@ -434,25 +360,12 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                 fi[t] = p;
                 np = 1u + p.c_new + p.c_inst + p.c_log;
             }
-            // exclusive scan of the piece counts over the workgroup
-            const uint32_t inc = wave_incl_scan(np, ScanSum32{});
-            if (l == kWave - 1) wtot[w] = inc;
-            __syncthreads();
-            uint32_t before = 0;
-            for (int x = 0; x < w; ++x) before += wtot[x];
-            poff[t] = before + inc - np;
-            if (t == kAbBlock - 1) poff[kAbBlock] = before + inc;
-            __syncthreads();
-            const uint32_t pieces = poff[kAbBlock];
+            const uint32_t pieces = piece_scan(np, poff, wtot, t);
             for (uint32_t p = t; p < pieces; p += kAbBlock) {
-                uint32_t fa = 0, fb = kAbBlock;  // the last item with poff <= p
-                while (fb - fa > 1) {
-                    const uint32_t mid = (fa + fb) >> 1;
-                    if (poff[mid] <= p) fa = mid; else fb = mid;
-                }
+                const uint32_t fa = piece_item(poff, p);
                 const AbPiece& F = fi[fa];
                 uint32_t k = p - poff[fa];
-                const uint32_t vn = ab_varint_len(F.n);
+                const uint32_t vn = varint_len(F.n);
                 const int64_t cs = F.start + kHead + vn;
                 if (k == 0) {  // the header and V(n); MIN: V(m) behind the commands
                     const uint32_t ld = (uint32_t)F.leader, in = (uint32_t)F.inst;
@@ -465,38 +378,38 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                     }
                     for (uint32_t x = 0; x < vn; ++x) {
                         const uint32_t at = kHead + x;
-                        h[at >> 2] |= ab_varint_byte(F.n, x) << (8 * (at & 3));
+                        h[at >> 2] |= varint_byte(F.n, x) << (8 * (at & 3));
                     }
-                    ab_or(W, F.start, h, kHead + vn);
+                    image_or<kAbWords>(W, F.start, h, kHead + vn);
                     if (MODE == MPX_MODE_MIN) {
-                        const uint32_t vm = ab_varint_len(F.m);
+                        const uint32_t vm = varint_len(F.m);
                         uint32_t v[2] = {0u, 0u};
                         for (uint32_t x = 0; x < vm; ++x)
-                            v[x >> 2] |= ab_varint_byte(F.m, x) << (8 * (x & 3));
-                        ab_or(W, cs + 17ll * F.n, v, vm);
+                            v[x >> 2] |= varint_byte(F.m, x) << (8 * (x & 3));
+                        image_or<kAbWords>(W, cs + 17ll * F.n, v, vm);
                     }
                     continue;
                 }
                 --k;
                 if (k < F.c_new) {  // a new command
                     const uint64_t j = F.cmd0 + k;
-                    ab_or_cmd(W, cs + 17ll * (F.j0 + k), a.op[j], (uint64_t)a.key[j],
+                    image_or_cmd<kAbWords>(W, cs + 17ll * (F.j0 + k), a.op[j], (uint64_t)a.key[j],
                               (uint64_t)a.val[j]);
                     continue;
                 }
                 k -= F.c_new;
                 // the CatchUpLog starts at ls; a record's bytes sit at ls + log_off[i] - L0
-                const int64_t ls = cs + 17ll * F.n + ab_varint_len(F.m);
+                const int64_t ls = cs + 17ll * F.n + varint_len(F.m);
                 if (k < F.c_inst) {  // a catch-up record's header
                     const uint64_t r = F.i0 + k;
                     const mpx_log_rec m = a.lrec[r];
                     if (m.status == MPX_STATUS_NIL) raise_err(err, kErrNil);
                     const uint64_t nc = a.lcoff[r + 1] - a.lcoff[r];
-                    const uint32_t vk = ab_varint_len(nc);
+                    const uint32_t vk = varint_len(nc);
                     uint32_t h[5] = {(uint32_t)m.ballot, (uint32_t)m.status, 0u, 0u, 0u};
                     for (uint32_t x = 0; x < vk; ++x)
-                        h[2 + (x >> 2)] |= ab_varint_byte(nc, x) << (8 * (x & 3));
-                    ab_or(W, ls + (int64_t)(a.log_off[r] - F.L0), h, 8 + vk);
+                        h[2 + (x >> 2)] |= varint_byte(nc, x) << (8 * (x & 3));
+                    image_or<kAbWords>(W, ls + (int64_t)(a.log_off[r] - F.L0), h, 8 + vk);
                     continue;
                 }
                 k -= F.c_inst;
@@ -509,7 +422,7 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
                     }
                     const uint64_t c0r = a.lcoff[ra], c1r = a.lcoff[ra + 1];
                     const uint64_t csr = a.log_off[ra + 1] - 17 * (c1r - c0r);
-                    ab_or_cmd(W, ls + (int64_t)(csr - F.L0) + 17ll * (int64_t)(j - c0r), a.lop[j],
+                    image_or_cmd<kAbWords>(W, ls + (int64_t)(csr - F.L0) + 17ll * (int64_t)(j - c0r), a.lop[j],
                               (uint64_t)a.lkey[j], (uint64_t)a.lval[j]);
                 }
             }
@@ -518,17 +431,7 @@ __global__ __launch_bounds__(kAbBlock) void k_ab_emit(AbArgs a, const uint64_t* 
             __syncthreads();  // fi and poff are rewritten by the next chunk
         }
         __syncthreads();
-        const uint32_t bytes = (uint32_t)(b1 - b0);
-        const uint8_t* S = reinterpret_cast<const uint8_t*>(W);
-        uint8_t* dst = out + b0;
-        if (((uintptr_t)dst & 15) == 0) {
-            const uint32_t nv = bytes / 16;
-            for (uint32_t i = t; i < nv; i += kAbBlock)
-                st_stream(reinterpret_cast<uint4*>(dst) + i, reinterpret_cast<const uint4*>(W)[i]);
-            for (uint32_t i = nv * 16 + t; i < bytes; i += kAbBlock) dst[i] = S[i];
-        } else {
-            for (uint32_t i = t; i < bytes; i += kAbBlock) dst[i] = S[i];
-        }
+        window_store(W, (uint32_t)(b1 - b0), out + b0, t);
         __syncthreads();  // the next window zeroes W
     }
 }
@@ -552,8 +455,8 @@ hipError_t ab_run(const AbArgs& a, const AbWork& w, uint64_t items, uint8_t* out
                   uint64_t* dest_off, uint32_t* err, hipStream_t stream) {
     k_ab_sizes<MODE><<<(unsigned)((items + kAbBlock - 1) / kAbBlock), kAbBlock, 0, stream>>>(
         a, items, w.frame_off, err);
-    const hipError_t r = device_scan(AbSizeIn{w.frame_off},
-                                     AbFrameOut{w.frame_off, dest_off, a.n_sends, items}, items,
+    const hipError_t r = device_scan(SizeIn{w.frame_off},
+                                     FrameOffOut{w.frame_off, dest_off, a.n_sends, items}, items,
                                      ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
     if (r != hipSuccess) return r;
     const uint64_t windows = (out_cap + kAbWindow - 1) / kAbWindow;
@@ -576,7 +479,7 @@ hipError_t launch_encode_accepts(int mode, int32_t nrep, const mpx_accept_batch*
     const uint64_t items = (uint64_t)nrep * b->n_sends;
     if (b->n_sends >= (1ull << 32) || n_inst > (1ull << 32)) return hipErrorInvalidValue;
     if (items == 0) {
-        k_ab_empty<<<1, 64, 0, stream>>>(dest_off, (uint32_t)nrep);
+        k_zero_u64<<<1, 64, 0, stream>>>(dest_off, (uint32_t)nrep + 1);
         return hipGetLastError();
     }
     Carver c(work);
@@ -603,7 +506,7 @@ hipError_t launch_encode_accepts(int mode, int32_t nrep, const mpx_accept_batch*
     a.thrifty = (b->flags & MPX_AB_THRIFTY) ? 1u : 0u;
     a.alive = b->alive_mask;
     if (mode != MPX_MODE_MIN) return ab_run<MPX_MODE_CLASSIC>(a, w, items, out, out_cap, dest_off, err, stream);
-    k_ab_zero<<<1, 1, 0, stream>>>(w.log_off);
+    k_zero_u64<<<1, 1, 0, stream>>>(w.log_off, 1);
     const hipError_t r = device_scan(AbRecBytes{b->log_cmd_off}, AbRecOut{w.log_off}, n_inst,
                                      ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
     if (r != hipSuccess) return r;

@@ -172,9 +172,32 @@ __device__ __forceinline__ void tile_walk(TileLds& S, const int4* __restrict__ r
     if (ebits) raise_err(err, ebits);
 }
 
-}  // namespace mpx
-
-namespace mpx {
+// ---- handlers with one int4 of state per instance (k_accept_handle, k_commit_handle) --------------
+// What such a handler's thread carries across tile_walk's calls
+struct TileState {
+    int64_t spec_idx = -1;  // the state loaded ahead for round 0 (tile_walk's pre)
+    int4 spec = make_int4(0, 0, 0, 0);
+    uint32_t round = 0;     // rounds of the current tile done by this thread
+    // tile_walk's pre: the state of the instance thread t most likely owns in round 0
+    __device__ __forceinline__ void preload(const int4* s4, int32_t inst0, int32_t base,
+                                            uint64_t n_inst, int t) {
+        round = 0;
+        spec_idx = (int64_t)inst0 - base + t;
+        if (spec_idx >= 0 && (uint64_t)spec_idx < n_inst) spec = ld_stream(s4 + spec_idx);
+    }
+    // the state of window index idx (inwin: it lies in the window; else a nil instance)
+    __device__ __forceinline__ int4 take(const int4* s4, bool inwin, int64_t idx) {
+        const int4 st = inwin ? (idx == spec_idx ? spec : ld_stream(s4 + idx))
+                              : make_int4(MPX_STATUS_NIL, 0, 0, 0);
+        spec_idx = -1;  // (later rounds of the tile load their own)
+        return st;
+    }
+    // counts a round; true after the tile's last (uniform: nh is the workgroup's)
+    __device__ __forceinline__ bool last_round(const TileLds& S) {
+        ++round;
+        return !(round * kTileBlock < S.nh);
+    }
+};
 
 // The instances without records that border an owned instance (window-relative index idx, next
 // instance with records nxt, both from tile_walk): (idx, nxt) clamped to the window [0, n_inst),
