@@ -122,7 +122,7 @@ extern "C" {
 #define MPX_E_BAD_ID (-6)       /* reply Id outside [0,N): reference indexes peerCommits   */
 #define MPX_E_KV_FULL (-7)      /* KV table capacity exceeded                              */
 #define MPX_E_NODEV (-8)        /* no GPU / HIP device unavailable                         */
-#define MPX_E_UNSUPPORTED (-9)  /* feature not built in / input beyond supported limits    */
+#define MPX_E_UNSUPPORTED (-9)  /* input beyond the supported limits                       */
 
 /* ---- enums (values mirror the reference) ---------------------------------------------- */
 /* minpaxosproto.InstanceStatus  src/minpaxosproto/minpaxosproto.go:8-15

@@ -1201,8 +1201,9 @@ int mpx_encode_replies(mpx_engine* e, const mpx_reply_rec* recs, size_t n, uint3
 
 // ---- the acceptor side: handleAccept and the AcceptReply bytes ------------------------------
 namespace {
-// the sizes both forms take (the host form checks them before it allocates)
-int accept_handle_shape(mpx_engine* e, size_t n, size_t n_inst, size_t n_groups, uint32_t ipg) {
+// the sizes the host and _dev forms of the acceptor and commit handlers take (the host forms check
+// them before they allocate)
+int window_limits(mpx_engine* e, size_t n, size_t n_inst, size_t n_groups, uint32_t ipg) {
     if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
         n_inst > (1ull << 32))
         return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
@@ -1219,7 +1220,7 @@ int mpx_accept_handle_dev(mpx_engine* e, const mpx_accept_msg* d_msgs, size_t n,
     if ((n && (!d_msgs || !d_replies || !d_reply_to || !d_effect)) ||
         (n_inst && (!d_st_in || !d_st_out)) || !d_groups)
         return fail(e, MPX_E_INVAL, "null argument");
-    CK(accept_handle_shape(e, n, n_inst, n_groups, ipg));
+    CK(window_limits(e, n, n_inst, n_groups, ipg));
     HIPCHK(e, mpx::launch_accept_handle(e->cfg.mode, d_msgs, n, d_st_in, d_st_out, n_inst,
                                         inst_base, d_groups, n_groups, ipg, e->cfg.n_replicas,
                                         d_replies, d_reply_to, d_effect, e->d_err,
@@ -1234,7 +1235,7 @@ int mpx_accept_handle(mpx_engine* e, const mpx_accept_msg* msgs, size_t n, mpx_a
     if (!e) return MPX_E_INVAL;
     if ((n && (!msgs || !replies || !reply_to || !effect)) || (n_inst && !st) || !groups)
         return fail(e, MPX_E_INVAL, "null argument");
-    CK(accept_handle_shape(e, n, n_inst, n_groups, ipg));
+    CK(window_limits(e, n, n_inst, n_groups, ipg));
     CK(begin(e));
     Stage L(e);
     const Slot s_msg = L.add(n * sizeof(mpx_accept_msg)),
@@ -1317,15 +1318,25 @@ int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
 }
 
 // ---- the proposer side: handlePropose and the Accept bytes -----------------------------------
-// (the launchers are weak: a build without proposer.hip validates and then answers
-// MPX_E_UNSUPPORTED)
 namespace {
-const char* const kNoProposer = "the proposer kernels are not built in";
-
 int propose_shape(mpx_engine* e, size_t n_groups, size_t n_inst, uint32_t ipg) {
     if (n_groups > (1ull << 32) || n_inst > (1ull << 32) ||
         (n_groups ? (!ipg || n_groups * (uint64_t)ipg != n_inst) : n_inst != 0))
         return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    return MPX_OK;
+}
+// what the host and _dev forms of the Accept encoder check alike
+int accept_batch_args(mpx_engine* e, const mpx_accept_batch* b, const void* out, size_t out_cap,
+                      const void* dest_off) {
+    if (!b || !dest_off || (out_cap && !out) || (b->n_sends && (!b->sends || !b->groups)))
+        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    CK(propose_shape(e, b->n_groups, b->n_groups * (size_t)b->ipg, b->ipg));
+    if (b->n_sends >= (1ull << 32))
+        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends per call");
+    if (b->n_sends && !b->n_groups) return fail(e, MPX_E_INVAL, "sends without a window");
+    if (e->cfg.mode == MPX_MODE_MIN && b->n_sends &&
+        (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
+        return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
     return MPX_OK;
 }
 
@@ -1355,8 +1366,6 @@ int mpx_propose_handle_dev(mpx_engine* e, mpx_proposer_group* d_groups, size_t n
     if (n_groups && (!d_groups || !d_prop_off || !d_send_off || !d_st || !d_sends))
         return fail(e, MPX_E_INVAL, "null argument");
     CK(propose_shape(e, n_groups, n_inst, ipg));
-    if (!mpx::launch_propose_handle)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_propose_handle: ") + kNoProposer);
     HIPCHK(e, mpx::launch_propose_handle(e->cfg.mode, d_groups, n_groups, d_prop_off, d_send_off,
                                          d_st, d_lb, n_inst, inst_base, ipg, e->cfg.n_replicas,
                                          d_sends, e->d_err, pick(e, stream)));
@@ -1391,8 +1400,6 @@ int mpx_propose_handle(mpx_engine* e, mpx_proposer_group* groups, size_t n_group
             (G.crt_instance < first || G.crt_instance >= first + (int64_t)ipg))
             return fail(e, MPX_E_NIL_INSTANCE, "crt_instance is outside its group's window");
     }
-    if (!mpx::launch_propose_handle)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_propose_handle: ") + kNoProposer);
     CK(begin(e));
     Stage L(e);
     const Slot s_grp = L.add(n_groups * sizeof(mpx_proposer_group)),
@@ -1424,8 +1431,6 @@ int mpx_encode_accepts_reserve(mpx_engine* e, size_t max_sends, size_t max_n_ins
     (void)max_log_cmds;  // (the built form keeps offsets only, no catch-up bytes)
     if (max_sends >= (1ull << 32) || max_n_inst > (1ull << 32))
         return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends over 2^32 instances per call");
-    if (!mpx::accepts_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
     return reserve(e, e->ab_work,
                    mpx::accepts_work_bytes((uint32_t)e->cfg.n_replicas, max_sends, max_n_inst));
 }
@@ -1433,18 +1438,8 @@ int mpx_encode_accepts_reserve(mpx_engine* e, size_t max_sends, size_t max_n_ins
 int mpx_encode_accepts_dev(mpx_engine* e, const mpx_accept_batch* b, uint8_t* d_out,
                            size_t out_cap, uint64_t* d_dest_off, void* stream) {
     if (!e) return MPX_E_INVAL;
-    if (!b || !d_dest_off || (out_cap && !d_out) || (b->n_sends && (!b->sends || !b->groups)))
-        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    CK(accept_batch_args(e, b, d_out, out_cap, d_dest_off));
     const size_t n_inst = b->n_groups * (size_t)b->ipg;
-    CK(propose_shape(e, b->n_groups, n_inst, b->ipg));
-    if (b->n_sends >= (1ull << 32))
-        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends per call");
-    if (b->n_sends && !b->n_groups) return fail(e, MPX_E_INVAL, "sends without a window");
-    if (e->cfg.mode == MPX_MODE_MIN && b->n_sends &&
-        (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
-        return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
-    if (!mpx::launch_encode_accepts || !mpx::accepts_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
     // (an empty call uses no scratch)
     CK(reserved(e, e->ab_work,
                 b->n_sends ? mpx::accepts_work_bytes((uint32_t)e->cfg.n_replicas, b->n_sends, n_inst)
@@ -1459,18 +1454,11 @@ int mpx_encode_accepts_dev(mpx_engine* e, const mpx_accept_batch* b, uint8_t* d_
 int mpx_encode_accepts(mpx_engine* e, const mpx_accept_batch* b, uint8_t* out, size_t out_cap,
                        uint64_t* dest_off) {
     if (!e) return MPX_E_INVAL;
-    if (!b || !dest_off || (out_cap && !out) || (b->n_sends && (!b->sends || !b->groups)))
-        return fail(e, MPX_E_INVAL, "null or invalid argument");
+    CK(accept_batch_args(e, b, out, out_cap, dest_off));
     const size_t n_inst = b->n_groups * (size_t)b->ipg;
-    CK(propose_shape(e, b->n_groups, n_inst, b->ipg));
-    if (b->n_sends >= (1ull << 32))
-        return fail(e, MPX_E_UNSUPPORTED, "at most 2^32-1 sends per call");
-    if (b->n_sends && !b->n_groups) return fail(e, MPX_E_INVAL, "sends without a window");
     const bool min = e->cfg.mode == MPX_MODE_MIN;
     const int32_t N = e->cfg.n_replicas;
     const bool thrifty = (b->flags & MPX_AB_THRIFTY) != 0;
-    if (min && b->n_sends && (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
-        return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
     // the device kernels trust the offsets and the ranges
     std::vector<uint32_t> nils;  // nils[i] = nil records among window records [0, i)
     if (min && b->n_sends) {
@@ -1510,8 +1498,6 @@ int mpx_encode_accepts(mpx_engine* e, const mpx_accept_batch* b, uint8_t* out, s
     }
     if (nil_hit)
         return fail(e, MPX_E_NIL_INSTANCE, "a nil instance inside a catch-up range");
-    if (!mpx::launch_encode_accepts || !mpx::accepts_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_accepts: ") + kNoProposer);
     CK(begin(e));
     if (b->n_sends)
         GROW(e, e->ab_work, mpx::accepts_work_bytes((uint32_t)N, b->n_sends, n_inst));
@@ -1559,10 +1545,7 @@ int mpx_encode_accepts(mpx_engine* e, const mpx_accept_batch* b, uint8_t* out, s
 }
 
 // ---- Accept / Commit / PrepareReply payloads: Unmarshal in a batch ---------------------------
-// (weak launchers, like the proposer's)
 namespace {
-const char* const kNoUnmarshal = "mpx_unmarshal_frames: the unmarshal kernels are not built in";
-
 int unmarshal_args(mpx_engine* e, const void* buf, size_t len, const void* var, size_t n_var,
                    const mpx_unmarshal_out* o, const void* res) {
     if (!o || !res || (len && !buf) || (n_var && (!var || !len)))
@@ -1593,7 +1576,6 @@ int mpx_unmarshal_frames_reserve(mpx_engine* e, size_t max_var, size_t max_log_i
     if (!e) return MPX_E_INVAL;
     CK(record_limit(e, max_var));
     CK(record_limit(e, max_log_inst));
-    if (!mpx::unmarshal_work_bytes) return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
     e->um_var_cap = std::max(e->um_var_cap, max_var);
     e->um_log_cap = std::max(e->um_log_cap, max_log_inst);
     return reserve(e, e->um_work, mpx::unmarshal_work_bytes(e->um_var_cap, e->um_log_cap));
@@ -1607,8 +1589,6 @@ int mpx_unmarshal_frames_dev(mpx_engine* e, const uint8_t* d_buf, size_t len,
     CK(unmarshal_args(e, d_buf, len, d_var, n_var, out, d_res));
     if ((uintptr_t)d_buf & 15)
         return fail(e, MPX_E_INVAL, "mpx_unmarshal_frames_dev: d_buf must be 16-byte aligned");
-    if (!mpx::launch_unmarshal || !mpx::unmarshal_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
     CK(reserved(e, e->um_work,
                 mpx::unmarshal_work_bytes(n_var, unmarshal_log_slots(e, n_var, len)),
                 "mpx_unmarshal_frames_dev", "mpx_unmarshal_frames_reserve(n_var, n_log_inst)"));
@@ -1649,8 +1629,6 @@ int mpx_unmarshal_frames(mpx_engine* e, const uint8_t* buf, size_t len, const mp
         n_cmds += f.n_cmds;
         n_log += f.n_log;
     }
-    if (!mpx::launch_unmarshal || !mpx::unmarshal_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, kNoUnmarshal);
     CK(begin(e));
     e->um_log_cap = std::max<size_t>(e->um_log_cap, n_log);
     GROW(e, e->um_work, mpx::unmarshal_work_bytes(n_var, unmarshal_log_slots(e, n_var, len)));
@@ -1718,23 +1696,13 @@ int mpx_unmarshal_frames(mpx_engine* e, const uint8_t* buf, size_t len, const mp
 }
 
 // ---- the commit side: handleCommit[Short], the Commit bytes, CommitShort records --------------
-// (weak launchers, like the proposer's)
 namespace {
-const char* const kNoCommit = "the commit kernels are not built in";
-
-// the sizes the host and _dev forms of the family share
-int commit_limits(mpx_engine* e, size_t n, size_t n_groups, size_t n_inst, uint32_t ipg) {
-    if (!ipg || !n_groups || n_groups > (1ull << 32) || n_groups * (uint64_t)ipg != n_inst ||
-        n_inst > (1ull << 32))
-        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
-    return record_limit(e, n);
-}
 int commit_batch_args(mpx_engine* e, const mpx_commit_batch* b, const void* out, size_t out_cap,
                       const void* dest_off) {
     if (!b || !dest_off || (out_cap && !out) || (b->n_sends && (!b->sends || !b->groups)))
         return fail(e, MPX_E_INVAL, "null or invalid argument");
     if (b->n_sends || b->n_groups)
-        CK(commit_limits(e, b->n_sends, b->n_groups, b->n_groups * (size_t)b->ipg, b->ipg));
+        CK(window_limits(e, b->n_sends, b->n_groups * (size_t)b->ipg, b->n_groups, b->ipg));
     return MPX_OK;
 }
 int gather_args(mpx_engine* e, const void* buf, size_t len, const void* other, size_t n_other,
@@ -1755,9 +1723,7 @@ int mpx_commit_handle_dev(mpx_engine* e, const mpx_accept_msg* d_msgs, size_t n,
     if (!e) return MPX_E_INVAL;
     if ((n && (!d_msgs || !d_effect)) || !d_st || !d_committed_upto)
         return fail(e, MPX_E_INVAL, "null argument");
-    CK(commit_limits(e, n, n_groups, n_inst, ipg));
-    if (!mpx::launch_commit_handle)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_commit_handle: ") + kNoCommit);
+    CK(window_limits(e, n, n_inst, n_groups, ipg));
     HIPCHK(e, mpx::launch_commit_handle(d_msgs, n, d_st, n_inst, inst_base, d_committed_upto,
                                         n_groups, ipg, d_effect, d_log_recs, e->d_err,
                                         pick(e, stream)));
@@ -1770,14 +1736,12 @@ int mpx_commit_handle(mpx_engine* e, const mpx_accept_msg* msgs, size_t n, mpx_a
     if (!e) return MPX_E_INVAL;
     if ((n && (!msgs || !effect)) || !st || !committed_upto)
         return fail(e, MPX_E_INVAL, "null argument");
-    CK(commit_limits(e, n, n_groups, n_inst, ipg));
+    CK(window_limits(e, n, n_inst, n_groups, ipg));
     for (size_t g = 0; g < n_groups; ++g) {
         const int64_t first = (int64_t)inst_base + (int64_t)(g * ipg);
         if (committed_upto[g] < first - 1 || committed_upto[g] > first + (int64_t)ipg - 1)
             return fail(e, MPX_E_INVAL, "committed_upto[g] outside [first_g - 1, first_g + ipg - 1]");
     }
-    if (!mpx::launch_commit_handle)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_commit_handle: ") + kNoCommit);
     CK(begin(e));
     Stage L(e);
     const Slot s_msg = L.add(n * sizeof(mpx_accept_msg)),
@@ -1802,8 +1766,6 @@ int mpx_encode_commits_reserve(mpx_engine* e, size_t max_sends, size_t max_other
     if (!e) return MPX_E_INVAL;
     CK(record_limit(e, max_sends));
     CK(record_limit(e, max_other));
-    if (!mpx::commits_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
     e->cm_send_cap = std::max(e->cm_send_cap, max_sends);
     e->cm_other_cap = std::max(e->cm_other_cap, max_other);
     return reserve(e, e->cm_work, mpx::commits_work_bytes((uint32_t)e->cfg.n_replicas,
@@ -1814,8 +1776,6 @@ int mpx_encode_commits_dev(mpx_engine* e, const mpx_commit_batch* b, uint8_t* d_
                            uint64_t* d_dest_off, void* stream) {
     if (!e) return MPX_E_INVAL;
     CK(commit_batch_args(e, b, d_out, out_cap, d_dest_off));
-    if (!mpx::launch_encode_commits || !mpx::commits_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
     // (an empty call uses no scratch)
     CK(reserved(e, e->cm_work,
                 b->n_sends ? mpx::commits_work_bytes((uint32_t)e->cfg.n_replicas, b->n_sends, 0) : 0,
@@ -1844,8 +1804,6 @@ int mpx_encode_commits(mpx_engine* e, const mpx_commit_batch* b, uint8_t* out, s
         const int32_t self = b->groups[(size_t)idx / b->ipg].self_id;
         if (self < 0 || self >= N) return fail(e, MPX_E_INVAL, "self_id outside [0, N)");
     }
-    if (!mpx::launch_encode_commits || !mpx::commits_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_encode_commits: ") + kNoCommit);
     CK(begin(e));
     if (b->n_sends) GROW(e, e->cm_work, mpx::commits_work_bytes((uint32_t)N, b->n_sends, 0));
     Stage L(e);
@@ -1886,8 +1844,6 @@ int mpx_gather_commit_shorts_dev(mpx_engine* e, const uint8_t* d_buf, size_t len
                    d_n_shorts));
     if ((uintptr_t)d_buf & 15)
         return fail(e, MPX_E_INVAL, "mpx_gather_commit_shorts_dev: d_buf must be 16-byte aligned");
-    if (!mpx::launch_gather_commit_shorts || !mpx::commits_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_gather_commit_shorts: ") + kNoCommit);
     CK(reserved(e, e->cm_work, n_other ? mpx::commits_work_bytes(1, 0, n_other) : 0,
                 "mpx_gather_commit_shorts_dev", "mpx_encode_commits_reserve(0, n_other)"));
     HIPCHK(e, mpx::launch_gather_commit_shorts(d_buf, len, d_other, n_other, d_n_other, d_msgs,
@@ -1909,8 +1865,6 @@ int mpx_gather_commit_shorts(mpx_engine* e, const uint8_t* buf, size_t len,
             return fail(e, MPX_E_INVAL, "a CommitShort frame lies outside [0, len)");
         ++want;
     }
-    if (!mpx::launch_gather_commit_shorts || !mpx::commits_work_bytes)
-        return fail(e, MPX_E_UNSUPPORTED, std::string("mpx_gather_commit_shorts: ") + kNoCommit);
     CK(begin(e));
     if (n_other) GROW(e, e->cm_work, mpx::commits_work_bytes(1, 0, n_other));
     const size_t k = std::min<uint64_t>(cap, want);

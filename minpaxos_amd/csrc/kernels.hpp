@@ -201,54 +201,50 @@ hipError_t launch_encode_accept_replies(
     uint32_t* err, hipStream_t stream);
 
 // ---- the proposer side (mpx_propose_handle, mpx_encode_accepts; proposer.hip) ---------------
-// Weak: a build of engine.cpp without proposer.hip links, and the entry points then return
-// MPX_E_UNSUPPORTED.
 // One launch: no scratch, no control words.
-__attribute__((weak)) hipError_t launch_propose_handle(
+hipError_t launch_propose_handle(
     int mode, mpx_proposer_group* groups, uint64_t n_groups, const uint64_t* prop_off,
     const uint64_t* send_off, mpx_acceptor_state* st, mpx_inst_state* lb, uint64_t n_inst,
     int32_t base, uint32_t ipg, int32_t nrep, mpx_accept_send* sends, uint32_t* err,
     hipStream_t stream);
-__attribute__((weak)) uint64_t accepts_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst,
-                                                  Carver&& c = Carver());
+uint64_t accepts_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst,
+                            Carver&& c = Carver());
 // b: a host struct of device pointers; nothing is written at or past out + out_cap
-__attribute__((weak)) hipError_t launch_encode_accepts(
+hipError_t launch_encode_accepts(
     int mode, int32_t nrep, const mpx_accept_batch* b, uint8_t* out, uint64_t out_cap,
     uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
 // ---- Accept / Commit / PrepareReply payloads (mpx_unmarshal_frames; unmarshal.hip) ----------
-// Weak, like the proposer's. Scratch for calls of up to n_var frames carrying up to n_log
-// catch-up instances in total.
-__attribute__((weak)) uint64_t unmarshal_work_bytes(uint64_t n_var, uint64_t n_log,
-                                                    Carver&& c = Carver());
+// Scratch for calls of up to n_var frames carrying up to n_log catch-up instances in total.
+uint64_t unmarshal_work_bytes(uint64_t n_var, uint64_t n_log, Carver&& c = Carver());
 // o: a host struct of device pointers; d_n_var (optional, device): min(*d_n_var, n_var) frames are
 // processed. log_scratch: the catch-up instances the scratch was sized for (work_bytes must cover
 // unmarshal_work_bytes(n_var, min(log_scratch, len / 9))). Never reads buf at or past len
 // rounded up to 16.
-__attribute__((weak)) hipError_t launch_unmarshal(
+hipError_t launch_unmarshal(
     int mode, const uint8_t* buf, uint64_t len, const mpx_var_frame* var, uint64_t n_var,
     const uint64_t* d_n_var, const mpx_unmarshal_out* o, mpx_unmarshal_result* res,
     uint64_t log_scratch, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
 // ---- the commit side (mpx_commit_handle, mpx_encode_commits, mpx_gather_commit_shorts;
 // commit.hip) -------------------------------------------------------------------------------
-// Weak, like the proposer's. The handler is two launches (the handlers, then the per-group
-// committedUpTo prefix over the states they left): no scratch, no control words.
-__attribute__((weak)) hipError_t launch_commit_handle(
+// The handler is two launches (the handlers, then the per-group committedUpTo prefix over the
+// states they left): no scratch, no control words.
+hipError_t launch_commit_handle(
     const mpx_accept_msg* msgs, uint64_t n, mpx_acceptor_state* st, uint64_t n_inst, int32_t base,
     int32_t* committed_upto, uint64_t n_groups, uint32_t ipg, uint8_t* effect, mpx_log_rec* log_recs,
     uint32_t* err, hipStream_t stream);
 // the family's scratch: an encode of n_sends slots to nrep destinations, a gather over n_other
 // frames (each launcher carves with its own call's sizes and 0 for the other's)
-__attribute__((weak)) uint64_t commits_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_other,
-                                                  Carver&& c = Carver());
+uint64_t commits_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_other,
+                            Carver&& c = Carver());
 // b: a host struct of device pointers; nothing is written at or past out + out_cap
-__attribute__((weak)) hipError_t launch_encode_commits(
+hipError_t launch_encode_commits(
     int32_t nrep, const mpx_commit_batch* b, uint8_t* out, uint64_t out_cap, uint64_t* dest_off,
     void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 // d_n_other (optional, device): min(*d_n_other, n_other) frames are processed. Never reads buf at
 // or past len rounded up to 16.
-__attribute__((weak)) hipError_t launch_gather_commit_shorts(
+hipError_t launch_gather_commit_shorts(
     const uint8_t* buf, uint64_t len, const mpx_peer_frame* other, uint64_t n_other,
     const uint64_t* d_n_other, mpx_accept_msg* msgs, int32_t* count, uint32_t* frame_index,
     uint64_t cap, uint64_t* n_shorts, void* work, uint64_t work_bytes, uint32_t* err,

@@ -4,9 +4,11 @@
 // (so stream and event order hold trivially) and events carry a host timestamp.
 //
 // Two builds (never shipped, never loaded by the product path):
-//   * default (tests/test_sanitize.py): the kernel launchers compute nothing but read their inputs
-//     and write patterns over their outputs (see "kernel launchers" below); engine.cpp's argument
-//     validation, staging and error paths run under ASan + UBSan.
+//   * default (tests/test_sanitize.py, tests/test_family_host.py): the kernel launchers compute
+//     nothing but read their inputs and write patterns over their outputs (see "kernel launchers"
+//     below); engine.cpp's argument validation, staging and error paths run under ASan + UBSan.
+// Every launcher and scratch-size function of kernels.hpp has its stand-in here, in both builds
+// (MPX_STUB_ORACLE only changes the group step), so engine.cpp links with no symbol left open.
 //   * -DMPX_STUB_ORACLE=1 (tests/test_dist.py, libmpx_stub.so): the group-step launchers run the
 //     CPU oracle (oracle/oracle.cpp, linked into the stub) and the RCCL calls really reduce across
 //     PROCESSES — every rank maps one /dev/shm segment named after the unique id, deposits its
@@ -24,6 +26,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -240,14 +243,17 @@ extern "C" int orc_group_step(int N, int mode, const mpx_group_batch* b, uint32_
 // abi_driver.cpp checks what comes back):
 //   * it reads every byte of every input array;
 //   * an in/out array that is not state (scalars, watermarks, ret / conf_prev of the group step)
-//     comes back with every byte inverted, which shows the copy in, the copy out and the extent;
+//     or that is updated in place (the proposer's groups / st / lb, the commit handler's st /
+//     committed_upto) comes back with every byte inverted, which shows the copy in, the copy out
+//     and the extent;
 //   * it fills output k (k = 0, 1, ... over the launcher's pure outputs, in signature order) with
 //     the byte 0xA0 + k over exactly the extent the kernel may write; optional outputs only
 //     when given;
 //   * state passed as st_in / st_out (or *_in / *_out tables) is copied across;
 //   * scratch is filled over its whole stated size;
-//   * offsets a host form reads back to size its second copy (the log encoder's rec_off, the
-//     AcceptReply encoder's dest_off) get real values instead of a pattern.
+//   * values a host form reads back to size its second copy (the log encoder's rec_off, the
+//     three frame encoders' dest_off, the unmarshal's result counts, the gather's *n_shorts) are
+//     real values instead of a pattern.
 namespace {
 volatile uint64_t g_sink;
 void touch(const void* p, size_t bytes) {
@@ -505,6 +511,157 @@ hipError_t launch_encode_accept_replies(int mode, const mpx_accept_reply* replie
     for (uint64_t d = 0; d <= n_dest; ++d) dest_off[d] = n * d / n_dest * frame;
     fill(out, n * frame, 0);
     if (n) scratch(work, work_bytes);
+    return hipSuccess;
+}
+// in place: groups, st, lb (optional); output: one slot per send_off[n_groups]
+hipError_t launch_propose_handle(int, mpx_proposer_group* groups, uint64_t n_groups,
+                                 const uint64_t* prop_off, const uint64_t* send_off,
+                                 mpx_acceptor_state* st, mpx_inst_state* lb, uint64_t n_inst,
+                                 int32_t, uint32_t, int32_t, mpx_accept_send* sends, uint32_t*,
+                                 hipStream_t) {
+    if (!n_groups) return hipSuccess;
+    touch(prop_off, (n_groups + 1) * sizeof(uint64_t));
+    touch(send_off, (n_groups + 1) * sizeof(uint64_t));
+    flip(groups, n_groups * sizeof(*groups));
+    flip(st, n_inst * sizeof(*st));
+    if (lb) flip(lb, n_inst * sizeof(*lb));
+    fill(sends, send_off[n_groups] * sizeof(*sends), 0);
+    return hipSuccess;
+}
+// the two Accept / Commit encoders' frames: every flagged send puts one frame of `frame` bytes in
+// every destination's run, so dest_off[q] = q * flagged * frame; out gets its pattern over
+// dest_off[nrep] bytes, and never at or past out_cap
+constexpr uint64_t kStubAcceptFrame = 24, kStubCommitFrame = MPX_COMMIT_SHORT_FRAME;
+static void stub_frames(uint64_t flagged, uint64_t frame, int32_t nrep, uint8_t* out, uint64_t out_cap,
+                 uint64_t* dest_off) {
+    for (int32_t q = 0; q <= nrep; ++q) dest_off[q] = (uint64_t)q * flagged * frame;
+    fill(out, dest_off[nrep] < out_cap ? dest_off[nrep] : out_cap, 0);
+}
+uint64_t accepts_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst, Carver&&) {
+    return 4 * nrep * n_sends + 4 * n_inst + 256;
+}
+// the command arrays are read (whole) when a flagged send carries commands, the log in MIN
+hipError_t launch_encode_accepts(int mode, int32_t nrep, const mpx_accept_batch* b, uint8_t* out,
+                                 uint64_t out_cap, uint64_t* dest_off, void* work,
+                                 uint64_t work_bytes, uint32_t*, hipStream_t) {
+    const uint64_t n_inst = b->n_groups * (uint64_t)b->ipg;
+    uint64_t flagged = 0;
+    bool cmds = false;
+    touch(b->sends, b->n_sends * sizeof(*b->sends));
+    for (uint64_t i = 0; i < b->n_sends; ++i)
+        if (b->sends[i].flags & MPX_PH_ACCEPT) ++flagged, cmds |= b->sends[i].n_cmds != 0;
+    if (b->n_sends) touch(b->groups, b->n_groups * sizeof(*b->groups));
+    if (cmds) {
+        touch(b->cmd_op, b->n_cmds);
+        touch(b->cmd_key, b->n_cmds * 8);
+        touch(b->cmd_val, b->n_cmds * 8);
+    }
+    if (mode == MPX_MODE_MIN && b->n_sends) {
+        touch(b->peer_commits, b->n_groups * nrep * sizeof(int32_t));
+        touch(b->log_recs, n_inst * sizeof(*b->log_recs));
+        touch(b->log_cmd_off, (n_inst + 1) * sizeof(uint64_t));
+        touch(b->log_op, b->n_log_cmds);
+        touch(b->log_key, b->n_log_cmds * 8);
+        touch(b->log_val, b->n_log_cmds * 8);
+    }
+    stub_frames(flagged, kStubAcceptFrame, nrep, out, out_cap, dest_off);
+    if (b->n_sends) scratch(work, work_bytes);
+    return hipSuccess;
+}
+uint64_t unmarshal_work_bytes(uint64_t n_var, uint64_t n_log, Carver&&) {
+    return 16 * n_var + 8 * n_log + 256;
+}
+// outputs in mpx_unmarshal_out's order (accepts 0xA0 .. log_val 0xAC), each over min(capacity,
+// count) elements; cmd_off / log_inst_off (n_var + 1 entries) and log_cmd_off (a start per written
+// log record and the end) only when given. res is real: the counts of the frames processed, and
+// n_log_cmds = one command per catch-up instance, at most log_cmd_cap
+hipError_t launch_unmarshal(int, const uint8_t* buf, uint64_t len, const mpx_var_frame* var,
+                            uint64_t n_var, const uint64_t* d_n_var, const mpx_unmarshal_out* o,
+                            mpx_unmarshal_result* res, uint64_t, void* work, uint64_t work_bytes,
+                            uint32_t*, hipStream_t) {
+    touch(buf, len);
+    touch(var, n_var * sizeof(*var));
+    mpx_unmarshal_result r{};
+    r.n_var = d_n_var && *d_n_var < n_var ? *d_n_var : n_var;
+    for (uint64_t i = 0; i < r.n_var; ++i) {
+        r.n_accepts += var[i].code == MPX_PEER_ACCEPT;
+        r.n_commits += var[i].code == MPX_PEER_COMMIT;
+        r.n_cmds += var[i].n_cmds;
+        r.n_log_inst += var[i].n_log;
+    }
+    r.n_log_cmds = std::min<uint64_t>(o->log_cmd_cap, r.n_log_inst);
+    const uint64_t na = std::min<uint64_t>(o->accept_cap, r.n_accepts),
+                   nc = std::min<uint64_t>(o->commit_cap, r.n_commits),
+                   m = std::min<uint64_t>(o->cmd_cap, r.n_cmds),
+                   li = std::min<uint64_t>(o->log_inst_cap, r.n_log_inst);
+    fill(o->accepts, na * sizeof(*o->accepts), 0);
+    fill(o->accept_last_committed, na * sizeof(int32_t), 1);
+    fill(o->commits, nc * sizeof(*o->commits), 2);
+    fill(o->cmd_off, (n_var + 1) * sizeof(uint64_t), 3);
+    fill(o->op, m, 4);
+    fill(o->key, m * 8, 5);
+    fill(o->val, m * 8, 6);
+    fill(o->log_inst_off, (n_var + 1) * sizeof(uint64_t), 7);
+    fill(o->log_recs, li * sizeof(*o->log_recs), 8);
+    fill(o->log_cmd_off, (li + 1) * sizeof(uint64_t), 9);
+    fill(o->log_op, r.n_log_cmds, 10);
+    fill(o->log_key, r.n_log_cmds * 8, 11);
+    fill(o->log_val, r.n_log_cmds * 8, 12);
+    *res = r;
+    scratch(work, work_bytes);
+    return hipSuccess;
+}
+// in place: st, committed_upto; outputs: effect, log_recs (optional)
+hipError_t launch_commit_handle(const mpx_accept_msg* msgs, uint64_t n, mpx_acceptor_state* st,
+                                uint64_t n_inst, int32_t, int32_t* committed_upto,
+                                uint64_t n_groups, uint32_t, uint8_t* effect, mpx_log_rec* log_recs,
+                                uint32_t*, hipStream_t) {
+    touch(msgs, n * sizeof(*msgs));
+    flip(st, n_inst * sizeof(*st));
+    flip(committed_upto, n_groups * sizeof(int32_t));
+    fill(effect, n, 0);
+    fill(log_recs, n * sizeof(*log_recs), 1);
+    return hipSuccess;
+}
+uint64_t commits_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_other, Carver&&) {
+    return 4 * nrep * n_sends + 8 * n_other + 256;
+}
+hipError_t launch_encode_commits(int32_t nrep, const mpx_commit_batch* b, uint8_t* out,
+                                 uint64_t out_cap, uint64_t* dest_off, void* work,
+                                 uint64_t work_bytes, uint32_t*, hipStream_t) {
+    uint64_t flagged = 0;
+    bool cmds = false;
+    touch(b->sends, b->n_sends * sizeof(*b->sends));
+    for (uint64_t i = 0; i < b->n_sends; ++i)
+        if (b->sends[i].flags & MPX_CS_SEND) ++flagged, cmds |= b->sends[i].n_cmds != 0;
+    if (b->n_sends) touch(b->groups, b->n_groups * sizeof(*b->groups));
+    if (cmds) {
+        touch(b->cmd_op, b->n_cmds);
+        touch(b->cmd_key, b->n_cmds * 8);
+        touch(b->cmd_val, b->n_cmds * 8);
+    }
+    stub_frames(flagged, kStubCommitFrame, nrep, out, out_cap, dest_off);
+    if (b->n_sends) scratch(work, work_bytes);
+    return hipSuccess;
+}
+// *n_shorts: the CommitShort codes among the frames processed; msgs, count, frame_index over
+// min(cap, *n_shorts) elements
+hipError_t launch_gather_commit_shorts(const uint8_t* buf, uint64_t len, const mpx_peer_frame* other,
+                                       uint64_t n_other, const uint64_t* d_n_other,
+                                       mpx_accept_msg* msgs, int32_t* count, uint32_t* frame_index,
+                                       uint64_t cap, uint64_t* n_shorts, void* work,
+                                       uint64_t work_bytes, uint32_t*, hipStream_t) {
+    touch(buf, len);
+    touch(other, n_other * sizeof(*other));
+    const uint64_t n = d_n_other && *d_n_other < n_other ? *d_n_other : n_other;
+    uint64_t shorts = 0;
+    for (uint64_t i = 0; i < n; ++i) shorts += other[i].code == MPX_PEER_COMMIT_SHORT;
+    const uint64_t k = shorts < cap ? shorts : cap;
+    fill(msgs, k * sizeof(*msgs), 0);
+    fill(count, k * sizeof(int32_t), 1);
+    fill(frame_index, k * sizeof(uint32_t), 2);
+    *n_shorts = shorts;
+    if (n_other) scratch(work, work_bytes);
     return hipSuccess;
 }
 uint64_t logenc_work_bytes(uint64_t n, uint64_t, Carver&&) { return 8 * n + 256; }

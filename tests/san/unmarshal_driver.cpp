@@ -1,32 +1,13 @@
 // tests/san/unmarshal_driver.cpp — TEST INFRASTRUCTURE ONLY: drives mpx_unmarshal_frames and its
 // _reserve / _dev forms of the CPU build of engine.cpp over the stub runtime (hip_stub.cpp) under
-// ASan + UBSan. The stub has no stand-ins for the unmarshal launchers, so the weak symbols stay
-// null: every validation path of the host form must answer its code before that is looked at,
-// and a valid call answers MPX_E_UNSUPPORTED. Exit status 0 = all checks passed.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
+// ASan + UBSan. Every validation path of the host form must answer its code (MPX_E_INVAL,
+// MPX_E_UNSUPPORTED for a size limit) before anything is staged; a valid call answers MPX_OK and,
+// over the stub's stand-ins for the unmarshal launchers, stages its arrays whole and apart (the
+// staging checks of san_check.hpp). Exit status 0 = all checks passed.
+#include <algorithm>
 #include <utility>
-#include <vector>
 
-#include "mpx.h"
-
-static int failures = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
-            ++failures;                                                    \
-        }                                                                  \
-    } while (0)
-// a failure on a live handle names its reason
-#define FAILS(e, call, code)                                   \
-    do {                                                       \
-        const int _rc = (call);                                \
-        if (_rc != (code)) fprintf(stderr, "  got %d: %s\n", _rc, mpx_last_error(e)); \
-        CHECK(_rc == (code));                                  \
-        CHECK(strlen(mpx_last_error(e)) > 0);                  \
-    } while (0)
+#include "san_check.hpp"
 
 static void put32(std::vector<uint8_t>& b, int32_t v) {
     for (int i = 0; i < 4; ++i) b.push_back((uint8_t)((uint32_t)v >> (8 * i)));
@@ -91,6 +72,103 @@ static void build(int mode, std::vector<uint8_t>& b, mpx_var_frame f[3]) {
     if (min) b.push_back(0);
     f[2].log_off = (uint32_t)b.size();
     f[2].length = (uint32_t)b.size() - f[2].offset;
+}
+
+// build()'s three frames `reps` times over, back to back
+static void build_many(int mode, size_t reps, std::vector<uint8_t>& b, std::vector<mpx_var_frame>& f) {
+    std::vector<uint8_t> one;
+    mpx_var_frame g[3];
+    build(mode, one, g);
+    for (size_t r = 0; r < reps; ++r) {
+        const uint32_t at = (uint32_t)b.size();
+        b.insert(b.end(), one.begin(), one.end());
+        for (mpx_var_frame x : g) {
+            x.offset += at;
+            x.cmds_off += at;
+            x.log_off += at;
+            f.push_back(x);
+        }
+    }
+}
+
+// A valid call over the first n_var of build()'s frames on guarded buffers. The stub counts the
+// frames as the kernel does and gives every catch-up instance one command, so: buf and var come
+// back intact, *res is complete, each output holds its pattern over min(capacity, count) elements
+// and the offset arrays over n_var + 1 (log_cmd_off: written records + 1) entries. offs: with
+// cmd_off / log_inst_off / log_cmd_off; arrays: with the other arrays (else null, capacities 0).
+struct Caps {
+    size_t acc, com, cmd, li, lc;
+};
+static void unmarshal_case(mpx_engine* e, const std::vector<uint8_t>& b,
+                           const mpx_var_frame* f, size_t n_var, Caps c, bool offs, bool arrays,
+                           bool dev) {
+    mpx_unmarshal_result want{};
+    for (size_t i = 0; i < n_var; ++i) {
+        want.n_accepts += f[i].code == MPX_PEER_ACCEPT;
+        want.n_commits += f[i].code == MPX_PEER_COMMIT;
+        want.n_cmds += f[i].n_cmds;
+        want.n_log_inst += f[i].n_log;
+    }
+    // the host form offers the kernel min(log_cmd_cap, len / 17) command slots
+    const size_t lm = dev ? c.lc : want.n_log_inst ? std::min(c.lc, b.size() / 17) : 0;
+    want.n_log_cmds = std::min<uint64_t>(lm, want.n_log_inst);
+    want.n_var = n_var;
+    const size_t na = std::min<uint64_t>(c.acc, want.n_accepts),
+                 nc = std::min<uint64_t>(c.com, want.n_commits),
+                 m = std::min<uint64_t>(c.cmd, want.n_cmds),
+                 li = std::min<uint64_t>(c.li, want.n_log_inst), lc = want.n_log_cmds;
+    // (the device form wants a 16-byte-aligned buffer: a vector's storage is)
+    In buf = holding(b.data(), b.size(), 1), var = holding(f, n_var, 2);
+    Out acc(c.acc * sizeof(mpx_accept_msg)), alc(c.acc * 4), com(c.com * sizeof(mpx_accept_msg)),
+        coff((n_var + 1) * 8), op(c.cmd), key(c.cmd * 8), val(c.cmd * 8), loff((n_var + 1) * 8),
+        lrec(c.li * sizeof(mpx_log_rec)), lcoff((c.li + 1) * 8), lop(c.lc), lkey(c.lc * 8),
+        lval(c.lc * 8), res(sizeof(mpx_unmarshal_result));
+    mpx_unmarshal_out o{};
+    if (arrays) {
+        o.accepts = acc.as<mpx_accept_msg>();
+        o.accept_last_committed = alc.as<int32_t>();
+        o.commits = com.as<mpx_accept_msg>();
+        o.op = op.as<uint8_t>();
+        o.key = key.as<int64_t>();
+        o.val = val.as<int64_t>();
+        o.log_recs = lrec.as<mpx_log_rec>();
+        o.log_op = lop.as<uint8_t>();
+        o.log_key = lkey.as<int64_t>();
+        o.log_val = lval.as<int64_t>();
+    }
+    o.accept_cap = c.acc;
+    o.commit_cap = c.com;
+    o.cmd_cap = c.cmd;
+    o.log_inst_cap = c.li;
+    o.log_cmd_cap = c.lc;
+    if (offs) {
+        o.cmd_off = coff.as<uint64_t>();
+        o.log_inst_off = loff.as<uint64_t>();
+        o.log_cmd_off = lcoff.as<uint64_t>();
+    }
+    if (dev)
+        CHECK(mpx_unmarshal_frames_dev(e, buf.as<uint8_t>(), b.size(), var.as<mpx_var_frame>(),
+                                       n_var, nullptr, &o, res.as<mpx_unmarshal_result>(),
+                                       nullptr) == MPX_OK);
+    else
+        CHECK(mpx_unmarshal_frames(e, buf.as<uint8_t>(), b.size(), var.as<mpx_var_frame>(), n_var,
+                                   &o, res.as<mpx_unmarshal_result>()) == MPX_OK);
+    CHECK(buf.intact() && var.intact());
+    CHECK(!memcmp(res.v.data(), &want, sizeof(want)));
+    for (size_t i = sizeof(want); i < res.v.size(); ++i) CHECK(res.v[i] == kGuardByte);
+    if (arrays) {
+        CHECK(acc.is(0, na * sizeof(mpx_accept_msg)) && alc.is(1, na * 4));
+        CHECK(com.is(2, nc * sizeof(mpx_accept_msg)));
+        CHECK(op.is(4, m) && key.is(5, m * 8) && val.is(6, m * 8));
+        CHECK(lrec.is(8, li * sizeof(mpx_log_rec)));
+        CHECK(lop.is(10, lc) && lkey.is(11, lc * 8) && lval.is(12, lc * 8));
+    } else {
+        CHECK(acc.untouched() && alc.untouched() && com.untouched() && op.untouched());
+        CHECK(key.untouched() && val.untouched() && lrec.untouched() && lop.untouched());
+        CHECK(lkey.untouched() && lval.untouched());
+    }
+    if (offs) CHECK(coff.is(3) && loff.is(7) && lcoff.is(9, (li + 1) * 8));
+    else CHECK(coff.untouched() && loff.untouched() && lcoff.untouched());
 }
 
 static void run(mpx_engine* e, int mode) {
@@ -211,23 +289,49 @@ static void run(mpx_engine* e, int mode) {
     reset();
     g[1] = g[0];
     FAILS(e, call(g, 3, b.size(), o), MPX_E_INVAL);
-    // valid calls: the kernels are not in this build
-    FAILS(e, call(f, 3, b.size(), o), MPX_E_UNSUPPORTED);
-    FAILS(e, call(f + 1, 2, b.size(), o), MPX_E_UNSUPPORTED);  // (gaps between frames are legal)
-    FAILS(e, call(f, 0, b.size(), o), MPX_E_UNSUPPORTED);
-    mpx_unmarshal_out none{};
-    FAILS(e, call(f, 3, b.size(), none), MPX_E_UNSUPPORTED);  // capacities of 0, null arrays
-    FAILS(e, mpx_unmarshal_frames(e, nullptr, 0, nullptr, 0, &none, &res), MPX_E_UNSUPPORTED);
-    FAILS(e, mpx_unmarshal_frames_reserve(e, 16, 16), MPX_E_UNSUPPORTED);
+    // a reserve beyond the record limit, and the device form: null arguments, a misaligned buffer
     FAILS(e, mpx_unmarshal_frames_reserve(e, (size_t)1 << 33, 16), MPX_E_UNSUPPORTED);
-    // the device form: null arguments, a misaligned buffer
     alignas(16) uint8_t ab[256];
     memcpy(ab, b.data(), b.size());
     FAILS(e, mpx_unmarshal_frames_dev(e, ab, b.size(), f, 3, nullptr, nullptr, &res, nullptr), MPX_E_INVAL);
     FAILS(e, mpx_unmarshal_frames_dev(e, ab, b.size(), f, 3, nullptr, &o, nullptr, nullptr), MPX_E_INVAL);
     FAILS(e, mpx_unmarshal_frames_dev(e, nullptr, b.size(), f, 3, nullptr, &o, &res, nullptr), MPX_E_INVAL);
     FAILS(e, mpx_unmarshal_frames_dev(e, ab + 8, b.size(), f, 3, nullptr, &o, &res, nullptr), MPX_E_INVAL);
-    FAILS(e, mpx_unmarshal_frames_dev(e, ab, b.size(), f, 3, nullptr, &o, &res, nullptr), MPX_E_UNSUPPORTED);
+    // the device form never allocates: it needs its reserve call first (no host form has run yet)
+    FAILS(e, mpx_unmarshal_frames_dev(e, ab, b.size(), f, 3, nullptr, &o, &res, nullptr), MPX_E_INVAL);
+    CHECK(strstr(mpx_last_error(e), "mpx_unmarshal_frames_dev") && strstr(mpx_last_error(e), "mpx_unmarshal_frames_reserve"));
+    CHECK(mpx_unmarshal_frames_reserve(e, 16, 16) == MPX_OK);
+    CHECK(mpx_unmarshal_frames_dev(e, ab, b.size(), f, 3, nullptr, &o, &res, nullptr) == MPX_OK);
+    CHECK(res.n_var == 3 && res.n_accepts == 1 && res.n_commits == 1 && res.n_cmds == 3);
+    const Caps all{2, 2, 4, 2, 4}, zero{0, 0, 0, 0, 0};
+    unmarshal_case(e, b, f, 3, all, true, true, true);
+    unmarshal_case(e, b, f, 3, zero, false, false, true);
+    // valid calls of the host form
+    CHECK(call(f, 3, b.size(), o) == MPX_OK);
+    CHECK(res.n_var == 3 && res.n_log_inst == (min ? 1u : 0u));
+    CHECK(call(f + 1, 2, b.size(), o) == MPX_OK && res.n_var == 2);  // (gaps between frames are legal)
+    CHECK(call(f, 0, b.size(), o) == MPX_OK && res.n_var == 0);
+    mpx_unmarshal_out none{};
+    CHECK(call(f, 3, b.size(), none) == MPX_OK && res.n_cmds == 3);  // capacities of 0, null arrays
+    CHECK(mpx_unmarshal_frames(e, nullptr, 0, nullptr, 0, &none, &res) == MPX_OK && res.n_var == 0);
+    // ... on guarded buffers: every array given; capacities below the counts (the log's command
+    // capacity above them: the second copy takes res->n_log_cmds of it); the offset arrays absent;
+    // capacities of 0 with null arrays; fewer frames and none
+    unmarshal_case(e, b, f, 3, all, true, true, false);
+    unmarshal_case(e, b, f, 3, Caps{0, 0, 2, 0, 3}, true, true, false);
+    unmarshal_case(e, b, f, 3, Caps{1, 1, 3, 1, 1}, true, true, false);
+    unmarshal_case(e, b, f, 3, all, false, true, false);
+    unmarshal_case(e, b, f, 3, zero, true, false, false);
+    unmarshal_case(e, b, f, 3, zero, false, false, false);
+    unmarshal_case(e, b, f, 1, all, true, true, false);
+    unmarshal_case(e, b, f, 0, all, true, true, false);
+    // ... and of a size at which the arrays have slots of more than one 256-byte unit
+    std::vector<uint8_t> bb;
+    std::vector<mpx_var_frame> ff;
+    build_many(mode, 100, bb, ff);
+    unmarshal_case(e, bb, ff.data(), 300, Caps{100, 100, 300, 100, 100}, true, true, false);
+    unmarshal_case(e, bb, ff.data(), 300, Caps{120, 80, 290, 120, 70}, true, true, false);
+    unmarshal_case(e, bb, ff.data(), 299, Caps{120, 120, 320, 120, 120}, false, true, false);
 }
 
 int main() {

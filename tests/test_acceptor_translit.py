@@ -137,6 +137,23 @@ def test_stub_build_exports_the_entry_points_without_the_kernels(stub_lib):
     assert lib.mpx_encode_accept_replies_reserve(None, 16) == R.E_INVAL
 
 
+def test_stub_build_exports_the_newer_families_entry_points(stub_lib):
+    """... and the proposer, unmarshal and commit entry points: their launchers have stand-ins in
+    the stub too, so the library loads with every symbol bound"""
+    lib = C.CDLL(stub_lib)
+    for name in ("mpx_propose_handle", "mpx_propose_handle_dev", "mpx_encode_accepts",
+                 "mpx_encode_accepts_reserve", "mpx_encode_accepts_dev",
+                 "mpx_unmarshal_frames", "mpx_unmarshal_frames_reserve", "mpx_unmarshal_frames_dev",
+                 "mpx_commit_handle", "mpx_commit_handle_dev", "mpx_encode_commits",
+                 "mpx_encode_commits_reserve", "mpx_encode_commits_dev",
+                 "mpx_gather_commit_shorts", "mpx_gather_commit_shorts_dev"):
+        assert hasattr(lib, name), name
+    lib.mpx_unmarshal_frames_reserve.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
+    assert lib.mpx_unmarshal_frames_reserve(None, 16, 16) == R.E_INVAL
+    lib.mpx_encode_commits_reserve.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
+    assert lib.mpx_encode_commits_reserve(None, 16, 16) == R.E_INVAL
+
+
 @pytest.mark.parametrize("mode", [R.MODE_MIN, R.MODE_CLASSIC], ids=["min", "classic"])
 def test_fuzz_generator_reaches_every_branch(mode):
     """every branch of the handler (and CLASSIC's requeue) is taken by at least 2 % of the
