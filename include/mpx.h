@@ -109,7 +109,8 @@ extern "C" {
                               mpx_accept_handle[_dev], mpx_encode_accept_replies[_reserve|_dev],
                               mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev],
                               mpx_unmarshal_frames[_reserve|_dev], mpx_commit_handle[_dev],
-                              mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev] */
+                              mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev],
+                              mpx_order_records[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1124,6 +1125,69 @@ int mpx_gather_commit_shorts_dev(mpx_engine* eng, const uint8_t* d_buf, size_t l
                                  const uint64_t* d_n_other, mpx_accept_msg* d_msgs,
                                  int32_t* d_count, uint32_t* d_frame_index, size_t cap,
                                  uint64_t* d_n_shorts, void* stream);
+
+/* ---- batch assembly: several connections' records as one legal handler batch ----------------
+ * Every handler above takes records grouped by instance, the groups ascending, slot order =
+ * arrival order (Contract). mpx_order_records produces that order from up to MPX_ORDER_MAX_SRC
+ * record arrays (one per connection, or the Commit and CommitShort lists of one stream): what the
+ * Go shim's sort.SliceStable by Instance over the arrival-ordered concatenation produces.
+ * Output order, ascending by these keys in turn: instance; arrival (when the call gives arrival
+ * keys); source index; index within the source.
+ *   out[n]   the records, 16 bytes each, bit-identical to the inputs (padding bytes included)
+ *   perm[n]  optional: for output slot i, the record's index in the concatenation of the sources
+ *            (the shim maps payloads and per-slot effects back with it)
+ *   *res     the result record below
+ * n_inst / inst_base: the window, as the handlers take it (1 <= n_inst <= 2^32; every instance of
+ * the window must be an int32). arrival_bits (0..32): the significant low bits of the arrival
+ * keys; 0 exactly when no source gives arrival keys.
+ * flags: MPX_ORDER_GENERAL takes the multi-launch radix path also for calls of at most
+ * MPX_ORDER_ONE_LAUNCH_MAX records, which otherwise run as one kernel in one workgroup; the results
+ * are the same (for tests and measurements).
+ * Errors: a record outside the window -> MPX_E_NIL_INSTANCE (the code the handlers answer for
+ * it), outputs unspecified; n_src > MPX_ORDER_MAX_SRC, n_inst outside its range, unknown flags,
+ * arrival keys given for some sources with records and not for others, arrival_bits > 32,
+ * arrival_bits set without keys or keys without arrival_bits, an arrival key with bits at or above
+ * arrival_bits (host form only) -> MPX_E_INVAL; 2^32-1 records or more in total ->
+ * MPX_E_UNSUPPORTED.                                                                              */
+#define MPX_ORDER_MAX_SRC 16
+#define MPX_ORDER_ONE_LAUNCH_MAX 4096
+#define MPX_ORDER_GENERAL 1u   /* call flag                                                      */
+#define MPX_ORD_WAS_ORDERED 1u /* result flag: the concatenated input was already in output order
+                                  (perm is the identity); without arrival keys that is: it already
+                                  met the handlers' contract                                     */
+typedef struct mpx_order_src {      /* one connection's / one list's records, in arrival order   */
+    const void* recs;               /* 16-byte records whose first field is int32 instance:
+                                       mpx_accept_reply or mpx_accept_msg                        */
+    const uint32_t* arrival;        /* optional per-record arrival key (e.g. the frame's stream
+                                       offset); given for every source of a call or for none     */
+    size_t n;
+} mpx_order_src;
+
+typedef struct mpx_order_result {
+    uint64_t n;        /* records written                                                        */
+    uint64_t n_runs;   /* distinct instances (= groups the handlers will see)                    */
+    int32_t lo, hi;    /* smallest / largest instance; lo = 0, hi = -1 when n == 0               */
+    uint32_t flags;    /* MPX_ORD_WAS_ORDERED                                                    */
+    uint32_t pad;
+} mpx_order_result;    /* 32 B */
+
+int mpx_order_records(mpx_engine* eng, const mpx_order_src* src, size_t n_src, size_t n_inst,
+                      int32_t inst_base, uint32_t arrival_bits, uint32_t flags, void* out,
+                      uint32_t* perm, mpx_order_result* res);
+/* scratch of mpx_order_records_dev calls of up to max_n records in total over windows of up to
+ * max_n_inst instances with any arrival_bits (grows only). The scratch and the family's control
+ * words live in the handle: the family's calls on one handle run in one stream order, and a
+ * larger reserve invalidates graphs captured before it.                                         */
+int mpx_order_records_reserve(mpx_engine* eng, size_t max_n, size_t max_n_inst);
+/* device form: src is a HOST array whose recs / arrival are device pointers (the n are host
+ * values); d_out must not overlap an input. Needs mpx_order_records_reserve first (a call of no
+ * record does not). Never allocates or synchronises; it captures into a graph. An out-of-window
+ * record is reported through the error word (MPX_E_NIL_INSTANCE at the next synchronising call);
+ * arrival keys are masked to arrival_bits. Alignment: recs and d_out 16 bytes; d_perm, arrival 4;
+ * d_res 8; any other address is rejected with MPX_E_INVAL.                                      */
+int mpx_order_records_dev(mpx_engine* eng, const mpx_order_src* src, size_t n_src, size_t n_inst,
+                          int32_t inst_base, uint32_t arrival_bits, uint32_t flags, void* d_out,
+                          uint32_t* d_perm, mpx_order_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

@@ -60,6 +60,15 @@ class MpxCommitBatch(C.Structure):
                 ("alive_mask", C.c_uint32)]
 
 
+class MpxOrderSrc(C.Structure):
+    _fields_ = [("recs", _p), ("arrival", _p), ("n", _sz)]
+
+
+class MpxOrderResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_runs", C.c_uint64), ("lo", C.c_int32), ("hi", C.c_int32),
+                ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -130,6 +139,11 @@ SIGNATURES = {
     "mpx_gather_commit_shorts": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _sz, _p]),
     "mpx_gather_commit_shorts_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _p, _sz, _p,
                                                _p]),
+    "mpx_order_records": (C.c_int, [_p, C.POINTER(MpxOrderSrc), _sz, _sz, _i32, C.c_uint32,
+                                    C.c_uint32, _p, _p, C.POINTER(MpxOrderResult)]),
+    "mpx_order_records_reserve": (C.c_int, [_p, _sz, _sz]),
+    "mpx_order_records_dev": (C.c_int, [_p, C.POINTER(MpxOrderSrc), _sz, _sz, _i32, C.c_uint32,
+                                        C.c_uint32, _p, _p, _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

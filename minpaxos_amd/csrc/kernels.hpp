@@ -250,6 +250,23 @@ hipError_t launch_gather_commit_shorts(
     uint64_t cap, uint64_t* n_shorts, void* work, uint64_t work_bytes, uint32_t* err,
     hipStream_t stream);
 
+// ---- batch assembly (mpx_order_records; order.hip) ------------------------------------------
+// Key bits of a call: ceil(log2(n_inst)) instance bits above arrival_bits arrival bits (<= 64).
+unsigned order_key_bits(uint64_t n_inst, uint32_t arrival_bits);
+// Scratch of a call of n records: the family's control words (the first kOrderCtlBytes, zeroed by
+// whoever allocates the buffer and left zero by every call), then the general path's keys,
+// permutation and sort scratch. wide: 64-bit keys (order_key_bits > 32); a wide carve-up of n
+// records holds every call of at most n.
+constexpr uint64_t kOrderCtlBytes = 256;
+uint64_t order_work_bytes(uint64_t n, bool wide, Carver&& c = Carver());
+// src: a host array of device pointers (validated by the caller: n_src <= MPX_ORDER_MAX_SRC, the
+// total below 2^32-1, arrival present for every source with records or for none). general: the
+// radix path also at or below MPX_ORDER_ONE_LAUNCH_MAX records.
+hipError_t launch_order_records(const mpx_order_src* src, uint32_t n_src, uint64_t n_inst,
+                                int32_t base, uint32_t arrival_bits, bool general, void* out,
+                                uint32_t* perm, mpx_order_result* res, void* work,
+                                uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

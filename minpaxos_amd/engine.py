@@ -20,6 +20,8 @@ Names and argument meaning follow the reference handlers they replace:
                          updateCommittedUpTo for a commit-only batch
   encode_commits      <- bcastCommit -> SendMsg: the CommitShort / Commit frames per peer
   gather_commit_shorts <- CommitShort.Unmarshal of the frames decode_stream listed
+  order_records       <- the shim's sort.SliceStable by Instance over the drained connections:
+                         the batch order every handler above asks for
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -675,6 +677,51 @@ class Engine:
                                                           d_n_other, d_msgs, d_count,
                                                           d_frame_index, cap, d_n_shorts, stream),
                     "mpx_gather_commit_shorts_dev")
+
+    # ---- batch assembly: several connections' records as one legal handler batch -------------
+    def order_records(self, sources, n_inst, inst_base=0, arrivals=None, arrival_bits=0,
+                      want_perm=True, general=False):
+        """sources: record arrays of one 16-byte dtype (ACCEPT_REPLY or ACCEPT_MSG), each in
+        arrival order; arrivals: None, or one uint32 array per source. Returns (records, perm
+        uint32 or None, result ORDER_RESULT scalar): the stable sort by instance (then arrival)
+        of the concatenation. general: R.ORDER_GENERAL, the radix path at any size."""
+        srcs = [np.ascontiguousarray(s) for s in sources]
+        dt = srcs[0].dtype if srcs else R.ACCEPT_REPLY
+        assert all(s.dtype == dt for s in srcs) and dt.itemsize == 16
+        arrs = [None] * len(srcs) if arrivals is None else \
+            [None if a is None else _c(a, np.uint32) for a in arrivals]
+        assert all(a is None or len(a) == len(s) for a, s in zip(arrs, srcs))
+        arr = (_lib.MpxOrderSrc * max(len(srcs), 1))()
+        for i, s in enumerate(srcs):
+            arr[i].recs, arr[i].n = _ptr(s) if len(s) else None, len(s)
+            arr[i].arrival = _ptr(arrs[i]) if len(s) else None
+        n = sum(len(s) for s in srcs)
+        out = np.zeros(max(n, 1), dt)
+        perm = np.zeros(max(n, 1), np.uint32) if want_perm else None
+        res = _lib.MpxOrderResult()
+        rc = self.lib.mpx_order_records(self.h, arr, len(srcs), n_inst, inst_base, arrival_bits,
+                                        R.ORDER_GENERAL if general else 0, _ptr(out), _ptr(perm),
+                                        C.byref(res))
+        self._check(rc, "mpx_order_records")
+        r = np.zeros((), R.ORDER_RESULT)
+        for f in R.ORDER_RESULT.names:
+            r[f] = getattr(res, f)
+        return out[:n], (perm[:n] if want_perm else None), r
+
+    def order_records_reserve(self, max_n, max_n_inst):
+        self._check(self.lib.mpx_order_records_reserve(self.h, max_n, max_n_inst),
+                    "mpx_order_records_reserve")
+
+    def order_records_dev(self, srcs, n_inst, inst_base, arrival_bits, d_out, d_perm, d_res,
+                          general=False, stream=None):
+        """srcs: (d_recs, d_arrival or None, n) per source, device pointers"""
+        arr = (_lib.MpxOrderSrc * max(len(srcs), 1))()
+        for i, (d_recs, d_arr, n) in enumerate(srcs):
+            arr[i].recs, arr[i].arrival, arr[i].n = d_recs, d_arr, n
+        rc = self.lib.mpx_order_records_dev(self.h, arr, len(srcs), n_inst, inst_base,
+                                            arrival_bits, R.ORDER_GENERAL if general else 0,
+                                            d_out, d_perm, d_res, stream)
+        self._check(rc, "mpx_order_records_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

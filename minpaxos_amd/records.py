@@ -126,6 +126,16 @@ COMMIT_SHORT_FRAME = 17
 assert COMMIT_SEND.itemsize == 32
 
 
+# batch assembly (mpx_order_records): mpx_order_result, the call flag and the result flag
+ORDER_RESULT = np.dtype([("n", "<u8"), ("n_runs", "<u8"), ("lo", "<i4"), ("hi", "<i4"),
+                         ("flags", "<u4"), ("pad", "<u4")])
+ORDER_MAX_SRC = 16
+ORDER_ONE_LAUNCH_MAX = 4096
+ORDER_GENERAL = 1
+ORD_WAS_ORDERED = 1
+assert ORDER_RESULT.itemsize == 32
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds
