@@ -49,6 +49,10 @@
  *                            mpx_encode_commits the CommitShort / Commit frames bcastCommit
  *                            (bareminpaxos.go:565-615 / paxos.go:336-386) writes to every peer;
  *                            mpx_gather_commit_shorts turns received CommitShort bodies into records
+ *   mpx_decode_client_streams <- genericsmr.(*Replica).clientListener (genericsmr.go:448-490) with
+ *                            Propose.Unmarshal (gsmrprotomarsh.go:65-80) for many client
+ *                            connections at once: the proposals as SoA commands, their reply
+ *                            metadata and the prop_off / send_off mpx_propose_handle_dev takes
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -82,13 +86,15 @@
  *     (mpx_apply_dev), group-step and durable-log replay (mpx_replay_durable_dev) kernels keep
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
  *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
- *     and the encoders and mpx_unmarshal_frames_dev keep their offsets and totals there:
+ *     and the encoders, mpx_unmarshal_frames_dev and mpx_decode_client_streams_dev keep their
+ *     offsets, maps and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
  *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
- *     mpx_unmarshal_frames_reserve, or a host-pointer mpx_apply / mpx_replay_durable /
- *     mpx_unmarshal_frames call that needs more) frees the old buffers and
+ *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve, or a host-pointer
+ *     mpx_apply / mpx_replay_durable / mpx_unmarshal_frames / mpx_decode_client_streams call that
+ *     needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
  *     returns MPX_E_NIL_INSTANCE / MPX_E_BAD_ID and the outputs are unspecified.
@@ -110,7 +116,8 @@ extern "C" {
                               mpx_propose_handle[_dev], mpx_encode_accepts[_reserve|_dev],
                               mpx_unmarshal_frames[_reserve|_dev], mpx_commit_handle[_dev],
                               mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev],
-                              mpx_order_records[_reserve|_dev] */
+                              mpx_order_records[_reserve|_dev],
+                              mpx_decode_client_streams[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1188,6 +1195,114 @@ int mpx_order_records_reserve(mpx_engine* eng, size_t max_n, size_t max_n_inst);
 int mpx_order_records_dev(mpx_engine* eng, const mpx_order_src* src, size_t n_src, size_t n_inst,
                           int32_t inst_base, uint32_t arrival_bits, uint32_t flags, void* d_out,
                           uint32_t* d_perm, mpx_order_result* d_res, void* stream);
+
+/* ---- client bytes in: batched Propose decode over many connections ---------------------------
+ * genericsmr.(*Replica).clientListener (genericsmr.go:448-490) reads one client connection as
+ * little-endian frames [code u8][body], after WaitForConnections consumed the connection-type byte
+ * (genericsmr.go:341-374; that byte is the caller's, never part of a connection here):
+ *   0 PROPOSE            30 B  CommandId i32, Op u8, K i64, V i64, Timestamp i64
+ *                              (gsmrprotomarsh.go:41-80, statemarsh.go:8-39) -> one proposal
+ *   2 READ               13 B  CommandId i32, Key i64 (:327-350): unmarshalled and dropped (:475)
+ *   4 PROPOSE_AND_READ   30 B  CommandId i32, Command 17 B, Key i64 (:267-292): dropped (:483)
+ *   any other byte        1 B  the switch has no default: the next byte is read as a code
+ * mpx_decode_client_streams frames many connections' unread bytes at once. A connection's bytes
+ * are buf[offset, offset + length); a frame whose body runs past them is a partial read
+ * (MPX_DECODE_PARTIAL): the caller keeps [consumed, length), as with the peer decoders. The
+ * reference ignores the error of Command.Unmarshal inside Propose.Unmarshal (:73), so a stream
+ * that ends inside a Propose's command can desynchronise it at EOF; the engine does not reproduce
+ * that: such a Propose is a partial read like any other.
+ * Outputs: the proposals connection by connection in conns order and in stream order inside a
+ * connection (one of the interleavings Go's goroutines may give, and a deterministic one).
+ * Proposal i is op[i], key[i], val[i] (the SoA layout of mpx_apply and mpx_accept_batch.cmd_*; the
+ * Op byte passes through whatever its value) and meta[i]; a proposal at or past prop_cap is not
+ * written (a capacity of 0 may come with null arrays), all counts are complete regardless.
+ * conn_res[k] is written for every connection. A stop in connection k has no effect on connection
+ * k + 1; bytes of buf outside every connection are never interpreted.
+ * conns: ascending by offset, non-overlapping, every offset a multiple of MPX_CLIENT_ALIGN, every
+ * connection inside [0, len] (a connection of length 0 is legal anywhere in the array); group
+ * non-decreasing and < n_groups, so connection order is already grouped by group.
+ *   prop_off[g]  (optional, n_groups + 1) the index of the first proposal of the first connection
+ *                with group >= g; prop_off[n_groups] the total
+ *   send_off[g]  (optional, n_groups + 1) exclusive prefix sums of ceil(n_g / MPX_PROPOSE_MAX_BATCH):
+ *                with prop_off the two trusted inputs of mpx_propose_handle_dev;
+ *                res->n_sends = send_off[n_groups] <= n_groups + len / 30 / 5000, the bound a
+ *                caller sizes `sends` with
+ * Limits: len <= MPX_DECODE_MAX_BYTES, n_conns <= MPX_CLIENT_MAX_CONNS, n_groups <=
+ * MPX_CLIENT_MAX_GROUPS, else MPX_E_UNSUPPORTED.
+ * Errors, host form, answered before anything is staged: null arguments; an offset not a multiple
+ * of MPX_CLIENT_ALIGN; a connection outside [0, len], overlapping or out of order; a group that
+ * decreases or is >= n_groups; prop_off or send_off given with n_groups == 0 -> MPX_E_INVAL.     */
+#define MPX_CLIENT_PROPOSE 0
+#define MPX_CLIENT_READ 2
+#define MPX_CLIENT_PROPOSE_AND_READ 4
+#define MPX_CLIENT_PROPOSE_FRAME 30
+#define MPX_CLIENT_READ_FRAME 13
+#define MPX_CLIENT_ALIGN 128          /* a connection's bytes start on a multiple of this        */
+#define MPX_CLIENT_MAX_CONNS (1u << 20)
+#define MPX_CLIENT_MAX_GROUPS (1u << 20)
+
+typedef struct mpx_client_conn {      /* one connection's unread bytes                           */
+    uint64_t offset;                  /* into buf, multiple of MPX_CLIENT_ALIGN                  */
+    uint32_t length;
+    uint32_t group;                   /* the group (Replica) it belongs to       */
+} mpx_client_conn;                    /* 16 B */
+
+typedef struct mpx_proposal {         /* bytes 8..23 of mpx_reply_rec, same field order          */
+    int64_t timestamp;
+    int32_t command_id;
+    uint32_t client;                  /* index in conns                                          */
+} mpx_proposal;                       /* 16 B */
+
+typedef struct mpx_client_conn_result {
+    uint64_t first;                   /* index of the connection's first proposal in the outputs */
+    uint32_t consumed;                /* bytes framed; the caller keeps [consumed, length)       */
+    uint32_t n_proposals;
+    uint32_t n_dropped;               /* READ, PROPOSE_AND_READ and 1-byte frames in [0, consumed) */
+    int32_t stop_reason;              /* MPX_DECODE_END / MPX_DECODE_PARTIAL                     */
+    int32_t stop_code;                /* code byte at consumed, -1 at MPX_DECODE_END             */
+    uint32_t pad;
+} mpx_client_conn_result;             /* 32 B */
+
+typedef struct mpx_client_result {
+    uint64_t n_proposals, n_dropped;  /* over all connections                                    */
+    uint64_t n_partial;               /* connections that stopped MPX_DECODE_PARTIAL             */
+    uint64_t n_sends;                 /* send_off[n_groups] (computed with or without send_off)  */
+} mpx_client_result;                  /* 32 B */
+
+typedef struct mpx_client_out {
+    uint8_t* op;
+    int64_t* key;
+    int64_t* val;
+    mpx_proposal* meta;
+    size_t prop_cap;
+    uint64_t* prop_off;               /* optional, n_groups + 1                                  */
+    uint64_t* send_off;               /* optional, n_groups + 1                                  */
+} mpx_client_out;
+
+int mpx_decode_client_streams(mpx_engine* eng, const uint8_t* buf, size_t len,
+                              const mpx_client_conn* conns, size_t n_conns, size_t n_groups,
+                              const mpx_client_out* out, mpx_client_conn_result* conn_res,
+                              mpx_client_result* res);
+/* scratch of mpx_decode_client_streams_dev calls on buffers of up to max_len bytes with up to
+ * max_conns connections and max_groups groups (grows only). The scratch and the family's control
+ * words live in the handle: the family's calls on one handle run in one stream order, and a
+ * larger reserve invalidates graphs captured before it.                                         */
+int mpx_decode_client_streams_reserve(mpx_engine* eng, size_t max_len, size_t max_conns,
+                                      size_t max_groups);
+/* device form: d_conns is a DEVICE array (a replayed graph sees new lengths every replay); out is a
+ * host struct of device pointers. Needs mpx_decode_client_streams_reserve first (a call with
+ * n_conns == 0 does not). Never allocates or synchronises; it captures into a graph. A connection
+ * with a misaligned offset, outside [0, len], with a group >= n_groups, or starting before the end
+ * / below the group of an earlier connection that passed the first three checks, is reported
+ * through the error word (MPX_E_INVAL at the next synchronising call) and frames nothing:
+ * consumed 0, counts 0, MPX_DECODE_END; the other connections are framed as if it were empty.
+ * Alignment: d_buf 16 bytes (it is loaded as 16-byte vectors and may be read up to len rounded up
+ * to 16, never at or past it); d_conns, out->meta, d_conn_res 16; offsets, keys, values, d_res 8;
+ * out->op any address; any other address is rejected with MPX_E_INVAL.                          */
+int mpx_decode_client_streams_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
+                                  const mpx_client_conn* d_conns, size_t n_conns, size_t n_groups,
+                                  const mpx_client_out* out, mpx_client_conn_result* d_conn_res,
+                                  mpx_client_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

@@ -69,6 +69,16 @@ class MpxOrderResult(C.Structure):
                 ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class MpxClientOut(C.Structure):
+    _fields_ = [("op", _p), ("key", _p), ("val", _p), ("meta", _p), ("prop_cap", _sz),
+                ("prop_off", _p), ("send_off", _p)]
+
+
+class MpxClientResult(C.Structure):
+    _fields_ = [("n_proposals", C.c_uint64), ("n_dropped", C.c_uint64),
+                ("n_partial", C.c_uint64), ("n_sends", C.c_uint64)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -144,6 +154,11 @@ SIGNATURES = {
     "mpx_order_records_reserve": (C.c_int, [_p, _sz, _sz]),
     "mpx_order_records_dev": (C.c_int, [_p, C.POINTER(MpxOrderSrc), _sz, _sz, _i32, C.c_uint32,
                                         C.c_uint32, _p, _p, _p, _p]),
+    "mpx_decode_client_streams": (C.c_int, [_p, _p, _sz, _p, _sz, _sz, C.POINTER(MpxClientOut),
+                                            _p, C.POINTER(MpxClientResult)]),
+    "mpx_decode_client_streams_reserve": (C.c_int, [_p, _sz, _sz, _sz]),
+    "mpx_decode_client_streams_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _sz,
+                                                C.POINTER(MpxClientOut), _p, _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

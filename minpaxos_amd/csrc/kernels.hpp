@@ -267,6 +267,19 @@ hipError_t launch_order_records(const mpx_order_src* src, uint32_t n_src, uint64
                                 uint32_t* perm, mpx_order_result* res, void* work,
                                 uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- client streams (mpx_decode_client_streams; client.hip) ----------------------------------
+// Scratch of a call on len bytes with n_conns connections and n_groups groups (no control words:
+// the family's kernels take no tickets and add no atomics); monotone in each argument.
+uint64_t client_work_bytes(uint64_t len, uint64_t n_conns, uint64_t n_groups, Carver&& c = Carver());
+// conns: a device array; out: a host struct of device pointers. Never reads buf at or past len
+// rounded up to 16. A call with n_conns == 0 uses no scratch.
+hipError_t launch_decode_client_streams(const uint8_t* buf, uint64_t len,
+                                        const mpx_client_conn* conns, uint64_t n_conns,
+                                        uint64_t n_groups, const mpx_client_out* out,
+                                        mpx_client_conn_result* conn_res, mpx_client_result* res,
+                                        void* work, uint64_t work_bytes, uint32_t* err,
+                                        hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

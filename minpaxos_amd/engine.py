@@ -22,6 +22,8 @@ Names and argument meaning follow the reference handlers they replace:
   gather_commit_shorts <- CommitShort.Unmarshal of the frames decode_stream listed
   order_records       <- the shim's sort.SliceStable by Instance over the drained connections:
                          the batch order every handler above asks for
+  decode_client_streams <- genericsmr.clientListener + Propose.Unmarshal over many connections:
+                         the proposals, their reply metadata and the per-group offsets
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -722,6 +724,64 @@ class Engine:
                                             arrival_bits, R.ORDER_GENERAL if general else 0,
                                             d_out, d_perm, d_res, stream)
         self._check(rc, "mpx_order_records_dev")
+
+    # ---- client bytes in: Propose decode over many connections --------------------------------
+    @staticmethod
+    def client_layout(bufs, groups=None):
+        """Lay per-connection byte strings out at R.CLIENT_ALIGN-byte offsets. Returns (buf uint8,
+        conns CLIENT_CONN)."""
+        conns = np.zeros(len(bufs), R.CLIENT_CONN)
+        at = 0
+        for k, b in enumerate(bufs):
+            conns[k] = (at, len(b), 0 if groups is None else groups[k])
+            at += -(-len(b) // R.CLIENT_ALIGN) * R.CLIENT_ALIGN
+        buf = np.zeros(at, np.uint8)
+        for k, b in enumerate(bufs):
+            o = int(conns["offset"][k])
+            buf[o:o + len(b)] = np.frombuffer(bytes(b), np.uint8)
+        return buf, conns
+
+    def decode_client_streams(self, bufs, groups=None, n_groups=1, prop_cap=None, buf=None,
+                              conns=None):
+        """bufs: one bytes per client connection (its unread bytes, after the connection-type
+        byte); groups: the connections' groups, non-decreasing. Or a ready layout (buf, conns).
+        Returns a dict: op, key, val, meta (PROPOSAL) trimmed to min(n_proposals, prop_cap),
+        prop_off, send_off (u64[n_groups + 1]), conn_res (CLIENT_CONN_RESULT per connection) and
+        res (CLIENT_RESULT scalar)."""
+        if buf is None:
+            buf, conns = self.client_layout(bufs, groups)
+        buf, conns = _c(buf, np.uint8), _c(conns, R.CLIENT_CONN)
+        n, nc = len(buf), len(conns)
+        cap = n // R.CLIENT_PROPOSE_FRAME if prop_cap is None else prop_cap
+        op, key, val = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.int64), \
+            np.zeros(max(cap, 1), np.int64)
+        meta = np.zeros(max(cap, 1), R.PROPOSAL)
+        po, so = np.zeros(n_groups + 1, np.uint64), np.zeros(n_groups + 1, np.uint64)
+        cres = np.zeros(max(nc, 1), R.CLIENT_CONN_RESULT)
+        out = _lib.MpxClientOut(_ptr(op), _ptr(key), _ptr(val), _ptr(meta), cap,
+                                _ptr(po) if n_groups else None, _ptr(so) if n_groups else None)
+        res = _lib.MpxClientResult()
+        rc = self.lib.mpx_decode_client_streams(self.h, _ptr(buf), n, _ptr(conns), nc, n_groups,
+                                                C.byref(out), _ptr(cres), C.byref(res))
+        self._check(rc, "mpx_decode_client_streams")
+        r = np.zeros((), R.CLIENT_RESULT)
+        for f in R.CLIENT_RESULT.names:
+            r[f] = getattr(res, f)
+        k = min(int(r["n_proposals"]), cap)
+        return dict(op=op[:k], key=key[:k], val=val[:k], meta=meta[:k], prop_off=po, send_off=so,
+                    conn_res=cres[:nc], res=r)
+
+    def decode_client_streams_reserve(self, max_len, max_conns, max_groups):
+        self._check(self.lib.mpx_decode_client_streams_reserve(self.h, max_len, max_conns,
+                                                               max_groups),
+                    "mpx_decode_client_streams_reserve")
+
+    def decode_client_streams_dev(self, d_buf, n, d_conns, n_conns, n_groups, out, d_conn_res,
+                                  d_res, stream=None):
+        """out: _lib.MpxClientOut of device pointers; d_conns: device CLIENT_CONN array"""
+        rc = self.lib.mpx_decode_client_streams_dev(self.h, d_buf, n, d_conns, n_conns, n_groups,
+                                                    C.byref(out), d_conn_res, d_res, stream)
+        self._check(rc, "mpx_decode_client_streams_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

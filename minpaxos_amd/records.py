@@ -136,6 +136,23 @@ ORD_WAS_ORDERED = 1
 assert ORDER_RESULT.itemsize == 32
 
 
+# the client side (mpx_decode_client_streams): frame codes of a client connection
+# (genericsmrproto.go:7-18), frame bytes with the code, and the four records of the call
+CLIENT_PROPOSE, CLIENT_READ, CLIENT_PROPOSE_AND_READ = 0, 2, 4
+CLIENT_PROPOSE_FRAME, CLIENT_READ_FRAME = 30, 13
+CLIENT_ALIGN = 128
+CLIENT_MAX_CONNS = CLIENT_MAX_GROUPS = 1 << 20
+CLIENT_CONN = np.dtype([("offset", "<u8"), ("length", "<u4"), ("group", "<u4")])
+PROPOSAL = np.dtype([("timestamp", "<i8"), ("command_id", "<i4"), ("client", "<u4")])
+CLIENT_CONN_RESULT = np.dtype([("first", "<u8"), ("consumed", "<u4"), ("n_proposals", "<u4"),
+                               ("n_dropped", "<u4"), ("stop_reason", "<i4"), ("stop_code", "<i4"),
+                               ("pad", "<u4")])
+CLIENT_RESULT = np.dtype([("n_proposals", "<u8"), ("n_dropped", "<u8"), ("n_partial", "<u8"),
+                          ("n_sends", "<u8")])
+assert CLIENT_CONN.itemsize == 16 and PROPOSAL.itemsize == 16
+assert CLIENT_CONN_RESULT.itemsize == 32 and CLIENT_RESULT.itemsize == 32
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds

@@ -132,6 +132,48 @@ def random_stream(proto, rng, n_frames, p_var=0.3, max_cmds=6, p_big=0.02, big_c
     return b"".join(out)
 
 
+# ---- client connections (genericsmrproto; gsmrprotomarsh.go) --------------------------------
+def propose(command_id, op, k, v, timestamp):
+    """Propose: CommandId i32, Command (Op u8, K i64, V i64), Timestamp i64    :41-63"""
+    return bytes([R.CLIENT_PROPOSE]) + struct.pack("<iBqqq", command_id, op, k, v, timestamp)
+
+
+def read(command_id, key):
+    """Read: CommandId i32, Key i64                                             :327-339"""
+    return bytes([R.CLIENT_READ]) + struct.pack("<iq", command_id, key)
+
+
+def propose_and_read(command_id, op, k, v, key):
+    """ProposeAndRead: CommandId i32, Command, Key i64                          :267-278"""
+    return bytes([R.CLIENT_PROPOSE_AND_READ]) + struct.pack("<iBqqq", command_id, op, k, v, key)
+
+
+def random_client_stream(rng, n_frames, p_read=0.08, p_par=0.08, p_unknown=0.1, p_zero=0.25):
+    """n_frames random frames of one client connection: Proposes (p_zero of them with an all-zero
+    payload, the rest with random fields, small ones among them so that payload bytes look like
+    codes), Reads, ProposeAndReads and 1-byte frames of an unknown code. Returns bytes."""
+    i64 = lambda: int(rng.integers(-(1 << 63), (1 << 63) - 1, endpoint=True))  # noqa: E731
+    i32 = lambda: int(rng.integers(-(1 << 31), 1 << 31))  # noqa: E731
+    small = lambda: int(rng.integers(0, 6))  # noqa: E731
+    out = []
+    for _ in range(n_frames):
+        u = rng.random()
+        val = i64 if rng.random() < 0.5 else small
+        if u < p_read:
+            out.append(read(i32(), val()))
+        elif u < p_read + p_par:
+            out.append(propose_and_read(i32(), int(rng.integers(0, 256)), val(), val(), val()))
+        elif u < p_read + p_par + p_unknown:
+            c = int(rng.integers(1, 256))
+            out.append(bytes([c if c not in (R.CLIENT_READ, R.CLIENT_PROPOSE_AND_READ) else 255]))
+        elif u < p_read + p_par + p_unknown + p_zero:
+            out.append(propose(0, 0, 0, 0, 0))
+        else:
+            out.append(propose(i32() if rng.random() < 0.5 else small(), int(rng.integers(0, 256)),
+                               val(), val(), val()))
+    return b"".join(out)
+
+
 def leader_stream(proto, recs, seed=61, prepare_every=4096, n_cmds=1, p_beacon=1.0 / 4096):
     """What a leader reads from one follower during recovery + steady state: every AcceptReply
     of `recs` (MIN 14-byte / CLASSIC 10-byte frames), a PrepareReply carrying n_cmds Commands
