@@ -53,6 +53,11 @@
  *                            Propose.Unmarshal (gsmrprotomarsh.go:65-80) for many client
  *                            connections at once: the proposals as SoA commands, their reply
  *                            metadata and the prop_off / send_off mpx_propose_handle_dev takes
+ *   mpx_build_replies     <- the three reply loops: handlePropose's refusals (bareminpaxos.go:
+ *                            622-623, :682-683 / paxos.go:390-391), handleAcceptReply with !Dreply
+ *                            (bareminpaxos.go:1030-1042 / paxos.go:644-655) and executeCommands
+ *                            with Dreply (bareminpaxos.go:1076-1084 / paxos.go:685-693): the
+ *                            mpx_reply_recs mpx_encode_replies takes, and bcastCommit's send list
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -86,14 +91,15 @@
  *     (mpx_apply_dev), group-step and durable-log replay (mpx_replay_durable_dev) kernels keep
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
  *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
- *     and the encoders, mpx_unmarshal_frames_dev and mpx_decode_client_streams_dev keep their
- *     offsets, maps and totals there:
+ *     and the encoders, mpx_unmarshal_frames_dev, mpx_decode_client_streams_dev and
+ *     mpx_build_replies_dev keep their offsets, maps and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
  *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
- *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve, or a host-pointer
- *     mpx_apply / mpx_replay_durable / mpx_unmarshal_frames / mpx_decode_client_streams call that
+ *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve /
+ *     mpx_build_replies_reserve, or a host-pointer mpx_apply / mpx_replay_durable /
+ *     mpx_unmarshal_frames / mpx_decode_client_streams / mpx_build_replies call that
  *     needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
@@ -117,7 +123,8 @@ extern "C" {
                               mpx_unmarshal_frames[_reserve|_dev], mpx_commit_handle[_dev],
                               mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev],
                               mpx_order_records[_reserve|_dev],
-                              mpx_decode_client_streams[_reserve|_dev] */
+                              mpx_decode_client_streams[_reserve|_dev],
+                              mpx_build_replies[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1053,7 +1060,8 @@ int mpx_commit_handle_dev(mpx_engine* eng, const mpx_accept_msg* d_msgs, size_t 
                           uint8_t* d_effect, mpx_log_rec* d_log_recs, void* stream);
 
 /* one decided instance whose Commit goes out: the leader fills the array from the tally's decided
- * mask, with MPX_CS_SEND on the decided slots (the others are skipped: no compaction needed)    */
+ * mask (mpx_build_replies does it on the device), with MPX_CS_SEND on the decided slots (the
+ * others are skipped: no compaction needed)                                                     */
 typedef struct mpx_commit_send {
     int32_t instance;
     int32_t ballot;
@@ -1303,6 +1311,99 @@ int mpx_decode_client_streams_dev(mpx_engine* eng, const uint8_t* d_buf, size_t 
                                   const mpx_client_conn* d_conns, size_t n_conns, size_t n_groups,
                                   const mpx_client_out* out, mpx_client_conn_result* d_conn_res,
                                   mpx_client_result* d_res, void* stream);
+
+/* ---- reply assembly: the client reply records from the sends, the masks, ret and meta ---------
+ * The three loops in which the reference answers its clients, as one expansion over data the
+ * other calls leave on the device (the mpx_accept_send slots of mpx_propose_handle, the tally's
+ * decided bytes, mpx_apply's ret, mpx_decode_client_streams' meta); what comes out is what
+ * mpx_encode_replies takes:
+ *   MPX_RB_FALSE     handlePropose's refusals         bareminpaxos.go:622-623, :682-683,
+ *                                                     paxos.go:390-391
+ *   MPX_RB_DECIDED   handleAcceptReply with !Dreply   bareminpaxos.go:1030-1042, paxos.go:644-655
+ *   MPX_RB_EXECUTED  executeCommands with Dreply      bareminpaxos.go:1076-1084, paxos.go:685-693
+ * Output order: send-array order, and inside a slot j = first_cmd .. first_cmd + n_cmds - 1. For
+ * sends as mpx_propose_handle writes them that is group by group with ascending instance, the
+ * order in which the reference's handlers and executeCommands reach them; the stable per-client
+ * fan-out of mpx_encode_replies keeps it.
+ *   MPX_RB_FALSE     a MPX_PH_NOT_LEADER slot emits one record per proposal, a MPX_PH_REFUSED slot
+ *                    one record, for its first proposal only: {value 0, timestamp 0, command_id -1,
+ *                    client = meta[j].client} (the Go writes ProposeReplyTS{FALSE, -1, state.NIL,
+ *                    0, ...}, not the proposal's own id and timestamp). mask, ret, ret_first and
+ *                    commit_sends must be null.
+ *   MPX_RB_DECIDED   eligible slots carry MPX_PH_ACCEPT or MPX_PH_PREPARE (an installed instance
+ *                    with client proposals; the caller passes no slot whose instance has
+ *                    ClientProposals == nil). A slot is selected when mask is null or
+ *                    mask[instance - inst_base] != 0; every proposal of a selected slot emits
+ *                    {0 (state.NIL), meta[j].timestamp, meta[j].command_id, meta[j].client}.
+ *                    ret and ret_first must be null.
+ *   MPX_RB_EXECUTED  the same selection; value = ret[(ret_first ? ret_first[s] : first_cmd) +
+ *                    (j - first_cmd)]. ret is required.
+ *   commit_sends     (optional; DECIDED and EXECUTED) every one of the n_sends entries is written,
+ *                    slot-aligned: {instance, ballot, first_cmd, n_cmds, flags = MPX_CS_SEND iff the
+ *                    slot is selected, pad 0}: CLASSIC's bcastCommit list, as mpx_encode_commits
+ *                    takes it. recs may then be null with cap == 0.
+ *   counts           res->n_replies and res->n_slots (the selected slots; MPX_RB_FALSE: the
+ *                    answering ones) are always complete; a record at or past cap is not written.
+ *                    With pad_client != MPX_RB_NO_PAD every slot of recs in [min(n_replies, cap),
+ *                    cap) is written {0, 0, 0, pad_client}: a captured chain encodes n = cap records
+ *                    with n_clients + 1 clients and pad_client = n_clients, and ignores the last
+ *                    run (mpx_encode_replies_dev takes a host n).
+ * flags: MPX_RB_GENERAL takes the multi-launch path also for calls of at most
+ * MPX_RB_ONE_LAUNCH_SLOTS slots and a cap of at most MPX_RB_ONE_LAUNCH_REPLIES records, which
+ * otherwise run as one kernel in one workgroup; the results are the same (for tests and
+ * measurements).
+ * Errors, host form, answered before anything is staged: null arguments, an unknown kind or flags,
+ * the kind's forbidden or missing arrays, reserved != 0, an eligible slot whose command range
+ * leaves [0, n_props) or whose result range leaves [0, n_ret) -> MPX_E_INVAL; with mask given, an
+ * eligible slot whose instance is outside the window -> MPX_E_NIL_INSTANCE; n_sends or the total
+ * at or above 2^32-1 -> MPX_E_UNSUPPORTED.                                                        */
+#define MPX_RB_FALSE 1u
+#define MPX_RB_DECIDED 2u
+#define MPX_RB_EXECUTED 3u
+#define MPX_RB_GENERAL 1u          /* call flag                                                  */
+#define MPX_RB_NO_PAD 0xFFFFFFFFu
+#define MPX_RB_ONE_LAUNCH_SLOTS 1024
+#define MPX_RB_ONE_LAUNCH_REPLIES 8192
+
+typedef struct mpx_reply_batch {
+    const mpx_accept_send* sends;  /* as mpx_propose_handle wrote them (or kept from earlier turns
+                                      / built by hand)                                           */
+    size_t n_sends;
+    int32_t inst_base;             /* the window mask is indexed by                              */
+    size_t n_inst;
+    const mpx_proposal* meta;      /* of the proposal arrays first_cmd indexes                   */
+    size_t n_props;
+    const uint8_t* mask;           /* optional, n_inst bytes by window index (the tally's decided
+                                      bytes, or an "executed" mask); NULL = every eligible slot  */
+    const int64_t* ret;            /* MPX_RB_EXECUTED: Execute's results                         */
+    size_t n_ret;
+    const uint64_t* ret_first;     /* optional, n_sends: where slot s's results start in ret (an
+                                      apply over gathered commands); NULL = first_cmd            */
+    uint32_t kind;                 /* MPX_RB_*                                                   */
+    uint32_t flags;                /* MPX_RB_GENERAL                                             */
+    uint32_t pad_client;           /* MPX_RB_NO_PAD, or the client index the tail is padded with */
+    uint32_t reserved;             /* 0                                                          */
+} mpx_reply_batch;
+
+typedef struct mpx_reply_result {
+    uint64_t n_replies, n_slots;
+} mpx_reply_result;                /* 16 B */
+
+int mpx_build_replies(mpx_engine* eng, const mpx_reply_batch* b, mpx_reply_rec* recs, size_t cap,
+                      mpx_commit_send* commit_sends, mpx_reply_result* res);
+/* scratch of mpx_build_replies_dev calls of up to max_sends slots (grows only). The scratch lives
+ * in the handle: the family's calls on one handle run in one stream order, and a larger reserve
+ * invalidates graphs captured before it.                                                        */
+int mpx_build_replies_reserve(mpx_engine* eng, size_t max_sends);
+/* device form: b is a host struct of device pointers. Needs mpx_build_replies_reserve first (a
+ * call with n_sends == 0 does not). Never allocates or synchronises; it captures into a graph. The
+ * per-slot conditions above are reported through the error word (the code arrives at the next
+ * synchronising call): such a slot emits nothing and its commit_sends flags are 0. Alignment:
+ * sends, meta, d_commit_sends 16 bytes; d_recs, ret, ret_first, d_res 8; mask any address; any
+ * other address is rejected with MPX_E_INVAL.                                                   */
+int mpx_build_replies_dev(mpx_engine* eng, const mpx_reply_batch* b, mpx_reply_rec* d_recs,
+                          size_t cap, mpx_commit_send* d_commit_sends, mpx_reply_result* d_res,
+                          void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

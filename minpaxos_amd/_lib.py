@@ -79,6 +79,17 @@ class MpxClientResult(C.Structure):
                 ("n_partial", C.c_uint64), ("n_sends", C.c_uint64)]
 
 
+class MpxReplyBatch(C.Structure):
+    _fields_ = [("sends", _p), ("n_sends", _sz), ("inst_base", C.c_int32), ("n_inst", _sz),
+                ("meta", _p), ("n_props", _sz), ("mask", _p), ("ret", _p), ("n_ret", _sz),
+                ("ret_first", _p), ("kind", C.c_uint32), ("flags", C.c_uint32),
+                ("pad_client", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MpxReplyResult(C.Structure):
+    _fields_ = [("n_replies", C.c_uint64), ("n_slots", C.c_uint64)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -159,6 +170,10 @@ SIGNATURES = {
     "mpx_decode_client_streams_reserve": (C.c_int, [_p, _sz, _sz, _sz]),
     "mpx_decode_client_streams_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _sz,
                                                 C.POINTER(MpxClientOut), _p, _p, _p]),
+    "mpx_build_replies": (C.c_int, [_p, C.POINTER(MpxReplyBatch), _p, _sz, _p,
+                                    C.POINTER(MpxReplyResult)]),
+    "mpx_build_replies_reserve": (C.c_int, [_p, _sz]),
+    "mpx_build_replies_dev": (C.c_int, [_p, C.POINTER(MpxReplyBatch), _p, _sz, _p, _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

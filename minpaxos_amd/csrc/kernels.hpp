@@ -280,6 +280,19 @@ hipError_t launch_decode_client_streams(const uint8_t* buf, uint64_t len,
                                         void* work, uint64_t work_bytes, uint32_t* err,
                                         hipStream_t stream);
 
+// ---- reply assembly (mpx_build_replies; replies.hip) ------------------------------------------
+// Scratch of a general-path call of n_sends slots (no control words: the family's kernels take no
+// tickets and add no atomics): the slots' reply counts and scanned offsets, the count blocks'
+// selected slots, the scan's tile totals; monotone in n_sends.
+uint64_t reply_work_bytes(uint64_t n_sends, Carver&& c = Carver());
+// b: a host struct of device pointers (validated by the caller: kind, flags, the kind's arrays,
+// n_sends below 2^32-1). One kernel in one workgroup with no scratch when n_sends <=
+// MPX_RB_ONE_LAUNCH_SLOTS, cap <= MPX_RB_ONE_LAUNCH_REPLIES and MPX_RB_GENERAL is not set; a call
+// with n_sends == 0 uses no scratch either. Nothing is written at or past recs + cap.
+hipError_t launch_build_replies(const mpx_reply_batch* b, mpx_reply_rec* recs, uint64_t cap,
+                                mpx_commit_send* commit_sends, mpx_reply_result* res, void* work,
+                                uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

@@ -24,8 +24,11 @@ Names and argument meaning follow the reference handlers they replace:
                          the batch order every handler above asks for
   decode_client_streams <- genericsmr.clientListener + Propose.Unmarshal over many connections:
                          the proposals, their reply metadata and the per-group offsets
+  build_replies       <- the three reply loops (handlePropose's refusals, handleAcceptReply with
+                         !Dreply, executeCommands with Dreply): the records encode_replies takes,
+                         and CLASSIC's bcastCommit list
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
-  encode_log          <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
+  encode_log         <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
 Errors come back as MpxError carrying the reference-level reason (e.g. E_NIL_INSTANCE where the
 Go handler would dereference a nil *Instance).
@@ -782,6 +785,58 @@ class Engine:
         rc = self.lib.mpx_decode_client_streams_dev(self.h, d_buf, n, d_conns, n_conns, n_groups,
                                                     C.byref(out), d_conn_res, d_res, stream)
         self._check(rc, "mpx_decode_client_streams_dev")
+
+    # ---- reply assembly: the client reply records from sends, masks, ret and meta --------------
+    def build_replies(self, kind, sends, meta, mask=None, inst_base=0, ret=None, ret_first=None,
+                      cap=None, pad_client=None, want_commit_sends=False, general=False):
+        """kind: R.RB_FALSE / RB_DECIDED / RB_EXECUTED; sends: ACCEPT_SEND; meta: PROPOSAL of the
+        proposal arrays first_cmd indexes; mask: optional uint8 per window index from inst_base;
+        ret: int64 (EXECUTED); ret_first: optional u64 per slot. cap: None = what the call needs
+        (with pad_client: that and one more). Returns (recs REPLY_REC trimmed to what was written,
+        commit_sends COMMIT_SEND or None, result REPLY_RESULT scalar)."""
+        sends, meta = _c(sends, R.ACCEPT_SEND), _c(meta, R.PROPOSAL)
+        mask = None if mask is None else _c(mask, np.uint8)
+        ret = None if ret is None else _c(ret, np.int64)
+        ret_first = None if ret_first is None else _c(ret_first, np.uint64)
+        n = len(sends)
+        if cap is None:
+            cap = int(sends["n_cmds"].astype(np.int64).sum()) + (pad_client is not None)
+        recs = np.zeros(max(cap, 1), R.REPLY_REC)
+        cs = np.zeros(max(n, 1), R.COMMIT_SEND) if want_commit_sends else None
+        b = _lib.MpxReplyBatch(_ptr(sends) if n else None, n, inst_base,
+                               0 if mask is None else len(mask), _ptr(meta) if len(meta) else None,
+                               len(meta), _ptr(mask), _ptr(ret), 0 if ret is None else len(ret),
+                               _ptr(ret_first), kind, R.RB_GENERAL if general else 0,
+                               R.RB_NO_PAD if pad_client is None else pad_client, 0)
+        res = _lib.MpxReplyResult()
+        rc = self.lib.mpx_build_replies(self.h, C.byref(b), _ptr(recs) if cap else None, cap,
+                                        _ptr(cs), C.byref(res))
+        self._check(rc, "mpx_build_replies")
+        r = np.zeros((), R.REPLY_RESULT)
+        r["n_replies"], r["n_slots"] = res.n_replies, res.n_slots
+        k = cap if pad_client is not None else min(int(res.n_replies), cap)
+        return recs[:k], (cs[:n] if want_commit_sends else None), r
+
+    def build_replies_reserve(self, max_sends):
+        self._check(self.lib.mpx_build_replies_reserve(self.h, max_sends),
+                    "mpx_build_replies_reserve")
+
+    def build_replies_dev(self, batch, d_recs, cap, d_commit_sends, d_res, stream=None):
+        """batch: _lib.MpxReplyBatch of device pointers (reply_batch_dev builds one)"""
+        self._check(self.lib.mpx_build_replies_dev(self.h, C.byref(batch), d_recs, cap,
+                                                   d_commit_sends, d_res, stream),
+                    "mpx_build_replies_dev")
+
+    @staticmethod
+    def reply_batch_dev(kind, d_sends, n_sends, d_meta, n_props, d_mask=None, n_inst=0,
+                        inst_base=0, d_ret=None, n_ret=0, d_ret_first=None, pad_client=None,
+                        general=False):
+        """the mpx_reply_batch of a build_replies_dev call; every d_* is a device pointer or a
+        devbuf.DevArray"""
+        p = [getattr(x, "ptr", x) for x in (d_sends, d_meta, d_mask, d_ret, d_ret_first)]
+        return _lib.MpxReplyBatch(p[0], n_sends, inst_base, n_inst, p[1], n_props, p[2], p[3],
+                                  n_ret, p[4], kind, R.RB_GENERAL if general else 0,
+                                  R.RB_NO_PAD if pad_client is None else pad_client, 0)
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

@@ -153,6 +153,16 @@ assert CLIENT_CONN.itemsize == 16 and PROPOSAL.itemsize == 16
 assert CLIENT_CONN_RESULT.itemsize == 32 and CLIENT_RESULT.itemsize == 32
 
 
+# reply assembly (mpx_build_replies): the kinds, the call flag, the one-launch bounds and
+# mpx_reply_result
+RB_FALSE, RB_DECIDED, RB_EXECUTED = 1, 2, 3
+RB_GENERAL = 1
+RB_NO_PAD = 0xFFFFFFFF
+RB_ONE_LAUNCH_SLOTS, RB_ONE_LAUNCH_REPLIES = 1024, 8192
+REPLY_RESULT = np.dtype([("n_replies", "<u8"), ("n_slots", "<u8")])
+assert REPLY_RESULT.itemsize == 16
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds
