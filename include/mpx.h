@@ -58,6 +58,8 @@
  *                            (bareminpaxos.go:1030-1042 / paxos.go:644-655) and executeCommands
  *                            with Dreply (bareminpaxos.go:1076-1084 / paxos.go:685-693): the
  *                            mpx_reply_recs mpx_encode_replies takes, and bcastCommit's send list
+ *   mpx_execute_gather    <- executeCommands' walk (bareminpaxos.go:1066-1098 / paxos.go:675-706):
+ *                            which instances run, and their commands gathered for mpx_apply
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -91,15 +93,16 @@
  *     (mpx_apply_dev), group-step and durable-log replay (mpx_replay_durable_dev) kernels keep
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
  *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
- *     and the encoders, mpx_unmarshal_frames_dev, mpx_decode_client_streams_dev and
- *     mpx_build_replies_dev keep their offsets, maps and totals there:
+ *     and the encoders, mpx_unmarshal_frames_dev, mpx_decode_client_streams_dev,
+ *     mpx_build_replies_dev and mpx_execute_gather_dev keep their offsets, maps and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
  *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
  *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve /
- *     mpx_build_replies_reserve, or a host-pointer mpx_apply / mpx_replay_durable /
- *     mpx_unmarshal_frames / mpx_decode_client_streams / mpx_build_replies call that
+ *     mpx_build_replies_reserve / mpx_execute_gather_reserve, or a host-pointer mpx_apply /
+ *     mpx_replay_durable / mpx_unmarshal_frames / mpx_decode_client_streams / mpx_build_replies /
+ *     mpx_execute_gather call that
  *     needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
@@ -124,7 +127,8 @@ extern "C" {
                               mpx_encode_commits[_reserve|_dev], mpx_gather_commit_shorts[_dev],
                               mpx_order_records[_reserve|_dev],
                               mpx_decode_client_streams[_reserve|_dev],
-                              mpx_build_replies[_reserve|_dev] */
+                              mpx_build_replies[_reserve|_dev],
+                              mpx_execute_gather[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1404,6 +1408,120 @@ int mpx_build_replies_reserve(mpx_engine* eng, size_t max_sends);
 int mpx_build_replies_dev(mpx_engine* eng, const mpx_reply_batch* b, mpx_reply_rec* d_recs,
                           size_t cap, mpx_commit_send* d_commit_sends, mpx_reply_result* d_res,
                           void* stream);
+
+/* ---- execute assembly: executeCommands' walk and the gather of its commands --------------------
+ * executeCommands (bareminpaxos.go:1066-1098 / paxos.go:675-706, the same code) walks every
+ * group's instances from the last executed one up to committedUpTo, stops at the first whose
+ * Cmds is nil and runs Execute on the others' commands in order. This call does the walk and
+ * gathers those commands, flat and in Execute's call order, for mpx_apply[_dev]; it leaves the
+ * "executed" mask and the ret_first array mpx_build_replies(MPX_RB_EXECUTED) takes. Instance
+ * numbers are window numbers as in mpx_commit_handle: idx = instance - inst_base belongs to group
+ * g = idx / ipg, n_inst == n_groups * ipg, first_g = inst_base + g * ipg, "none" is first_g - 1.
+ * Per group g, sequentially:
+ *     i = executed_in[g] + 1
+ *     while i <= committed_upto[g] and inst[i - inst_base].flags & MPX_IC_HAS_CMDS:
+ *         the instance executes: its commands src[first_cmd .. first_cmd + n_cmds) are appended
+ *         i++
+ *     executed_out[g] = i - 1
+ * executed_in[g] >= committed_upto[g] is legal and does nothing (MIN assigns committedUpTo =
+ * areply.Instance: it can move down). A nil instance at or below committedUpTo, where the Go
+ * dereferences nil, stops the walk like Cmds == nil (flags == 0 stands for both; the group step's
+ * has_cmds has the same convention). n_cmds == 0 with MPX_IC_HAS_CMDS is an empty non-nil slice: it
+ * executes nothing and the walk goes on.
+ * Output order: group by group, ascending instance, inside an instance first_cmd .. first_cmd +
+ * n_cmds - 1.
+ *   mask[n_inst]             required; every byte written, 1 exactly for the instances executed
+ *                            in this call
+ *   inst_first[n_inst]       optional; the exclusive sum of the executed instances' n_cmds before
+ *                            window slot idx, written for every slot
+ *   ret_first[n_sends]       optional, needs sends; inst_first[sends[s].instance - inst_base] for a
+ *                            send whose instance is in the window, else 0: mpx_reply_batch.ret_first
+ *   grp_cmd_off[n_groups+1]  optional; the offset of group g's first gathered command, entry
+ *                            n_groups the total
+ *   counts                   res is always complete, also past cap; a command at or past cap is
+ *                            not written (executed_in / executed_out are separate so that a short
+ *                            call can be repeated with a larger cap)
+ *   MPX_XG_PAD               every position j in [min(n_cmds, cap), cap) is written {op 0
+ *                            (state.NONE), key j, val 0}: Execute of NONE returns NIL and touches
+ *                            nothing (state.go:85-102), so a captured chain calls mpx_apply_dev(m =
+ *                            cap) and ignores the tail of ret; the key is j so that the pad does not
+ *                            pile onto one key's list in the apply kernels
+ *   MPX_XG_GENERAL           takes the multi-launch path also for calls of at most
+ *                            MPX_XG_ONE_LAUNCH_INST slots and a cap of at most
+ *                            MPX_XG_ONE_LAUNCH_CMDS, which otherwise run as one kernel in one
+ *                            workgroup; the results are the same (for tests and measurements)
+ * Errors, host form, answered before anything is staged: null required arrays, n_inst != n_groups *
+ * ipg (or ipg == 0 with groups), unknown flags, reserved != 0, ret_first without sends ->
+ * MPX_E_INVAL; committed_upto[g] or executed_in[g] outside [first_g - 1, first_g + ipg - 1] ->
+ * MPX_E_INVAL; an instance that executes whose [first_cmd, first_cmd + n_cmds) leaves [0, n_src) ->
+ * MPX_E_INVAL; n_inst or the gathered total at or above 2^32-1 -> MPX_E_UNSUPPORTED.            */
+#define MPX_IC_HAS_CMDS 1u         /* mpx_inst_cmds.flags: Cmds != nil                            */
+#define MPX_XG_PAD 1u              /* call flags                                                 */
+#define MPX_XG_GENERAL 2u
+#define MPX_XG_ONE_LAUNCH_INST 1024
+#define MPX_XG_ONE_LAUNCH_CMDS 8192
+
+/* where a window slot's Cmds live in the caller's persistent SoA command arrays */
+typedef struct mpx_inst_cmds {
+    uint64_t first_cmd;
+    uint32_t n_cmds;
+    uint32_t flags;                /* MPX_IC_HAS_CMDS; 0 = Cmds == nil, or a nil instance        */
+} mpx_inst_cmds;                   /* 16 B */
+
+typedef struct mpx_execute_batch {
+    const mpx_inst_cmds* inst;     /* n_inst, one per window slot                                */
+    size_t n_inst;
+    int32_t inst_base;
+    uint32_t ipg;
+    size_t n_groups;
+    const int32_t* committed_upto; /* n_groups                                                   */
+    const int32_t* executed_in;    /* n_groups: last executed instance, first_g - 1 = none       */
+    int32_t* executed_out;         /* n_groups; may alias executed_in                            */
+    const uint8_t* src_op;         /* the source commands, n_src                                 */
+    const int64_t* src_key;
+    const int64_t* src_val;
+    size_t n_src;
+    const mpx_accept_send* sends;  /* optional: the slots ret_first is written for               */
+    size_t n_sends;
+    uint32_t flags;                /* MPX_XG_*                                                   */
+    uint32_t reserved;             /* 0                                                          */
+} mpx_execute_batch;
+
+typedef struct mpx_execute_out {
+    uint8_t* op;                   /* the gathered commands, cap each                            */
+    int64_t* key;
+    int64_t* val;
+    size_t cap;
+    uint8_t* mask;                 /* n_inst                                                     */
+    uint64_t* inst_first;          /* optional, n_inst                                           */
+    uint64_t* ret_first;           /* optional, n_sends                                          */
+    uint64_t* grp_cmd_off;         /* optional, n_groups + 1                                     */
+} mpx_execute_out;
+
+typedef struct mpx_execute_result {
+    uint64_t n_cmds;               /* commands gathered (complete, also past cap)                */
+    uint64_t n_inst;               /* instances executed                                         */
+    uint64_t n_groups;             /* groups whose cursor moved                                  */
+    uint64_t reserved;             /* written 0                                                  */
+} mpx_execute_result;              /* 32 B */
+
+int mpx_execute_gather(mpx_engine* eng, const mpx_execute_batch* b, const mpx_execute_out* out,
+                       mpx_execute_result* res);
+/* scratch of mpx_execute_gather_dev calls of up to max_n_inst slots in up to max_n_groups groups
+ * (grows only). The scratch lives in the handle and holds one word per group between calls, which
+ * this call initialises: the family's calls on one handle run in one stream order, and a larger
+ * reserve invalidates graphs captured before it.                                               */
+int mpx_execute_gather_reserve(mpx_engine* eng, size_t max_n_inst, size_t max_n_groups);
+/* device form: b and out are host structs of device pointers. Needs mpx_execute_gather_reserve
+ * first. Never allocates or synchronises, needs no memset on the stream; it captures into a graph.
+ * The per-group and per-instance conditions above are reported through the error word (the code
+ * arrives at the next synchronising call): such a group does nothing (executed_out[g] =
+ * executed_in[g]), such an instance executes with no commands; every store stays inside its
+ * array. The total is not bounded here. Alignment: inst and sends 16 bytes; src_key, src_val, key,
+ * val, inst_first, ret_first, grp_cmd_off and d_res 8; committed_upto and executed_* 4; src_op, op
+ * and mask any address; any other address is rejected with MPX_E_INVAL.                        */
+int mpx_execute_gather_dev(mpx_engine* eng, const mpx_execute_batch* b, const mpx_execute_out* out,
+                           mpx_execute_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

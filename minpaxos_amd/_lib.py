@@ -90,6 +90,24 @@ class MpxReplyResult(C.Structure):
     _fields_ = [("n_replies", C.c_uint64), ("n_slots", C.c_uint64)]
 
 
+class MpxExecuteBatch(C.Structure):
+    _fields_ = [("inst", _p), ("n_inst", _sz), ("inst_base", C.c_int32), ("ipg", C.c_uint32),
+                ("n_groups", _sz), ("committed_upto", _p), ("executed_in", _p),
+                ("executed_out", _p), ("src_op", _p), ("src_key", _p), ("src_val", _p),
+                ("n_src", _sz), ("sends", _p), ("n_sends", _sz), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MpxExecuteOut(C.Structure):
+    _fields_ = [("op", _p), ("key", _p), ("val", _p), ("cap", _sz), ("mask", _p),
+                ("inst_first", _p), ("ret_first", _p), ("grp_cmd_off", _p)]
+
+
+class MpxExecuteResult(C.Structure):
+    _fields_ = [("n_cmds", C.c_uint64), ("n_inst", C.c_uint64), ("n_groups", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -174,6 +192,11 @@ SIGNATURES = {
                                     C.POINTER(MpxReplyResult)]),
     "mpx_build_replies_reserve": (C.c_int, [_p, _sz]),
     "mpx_build_replies_dev": (C.c_int, [_p, C.POINTER(MpxReplyBatch), _p, _sz, _p, _p, _p]),
+    "mpx_execute_gather": (C.c_int, [_p, C.POINTER(MpxExecuteBatch), C.POINTER(MpxExecuteOut),
+                                     C.POINTER(MpxExecuteResult)]),
+    "mpx_execute_gather_reserve": (C.c_int, [_p, _sz, _sz]),
+    "mpx_execute_gather_dev": (C.c_int, [_p, C.POINTER(MpxExecuteBatch),
+                                         C.POINTER(MpxExecuteOut), _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

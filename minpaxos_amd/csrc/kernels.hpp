@@ -293,6 +293,22 @@ hipError_t launch_build_replies(const mpx_reply_batch* b, mpx_reply_rec* recs, u
                                 mpx_commit_send* commit_sends, mpx_reply_result* res, void* work,
                                 uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- execute assembly (mpx_execute_gather; execute.hip) ---------------------------------------
+// Scratch of a general-path call of n_inst slots on a handle reserved for group_cap groups: first
+// the groups' stop words (group_cap of them, at the base whatever the call's sizes, kXgNoStop
+// between calls: the reserve call fills them, the call's last kernel puts them back), then the
+// slots' lengths and scanned offsets, the group blocks' partial counts and the scan's tile
+// totals; monotone in both arguments.
+constexpr uint32_t kXgNoStop = 0xFFFFFFFFu;
+uint64_t execute_work_bytes(uint64_t n_inst, uint64_t group_cap, Carver&& c = Carver());
+// b, out: host structs of device pointers (validated by the caller: the flags, the required
+// arrays, n_inst == n_groups * ipg below 2^32-1, n_groups <= group_cap). One kernel in one
+// workgroup with no scratch when n_inst <= MPX_XG_ONE_LAUNCH_INST, cap <= MPX_XG_ONE_LAUNCH_CMDS
+// and MPX_XG_GENERAL is not set. Nothing is written at or past an array's end.
+hipError_t launch_execute_gather(const mpx_execute_batch* b, const mpx_execute_out* out,
+                                 mpx_execute_result* res, void* work, uint64_t work_bytes,
+                                 uint64_t group_cap, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

@@ -27,6 +27,8 @@ Names and argument meaning follow the reference handlers they replace:
   build_replies       <- the three reply loops (handlePropose's refusals, handleAcceptReply with
                          !Dreply, executeCommands with Dreply): the records encode_replies takes,
                          and CLASSIC's bcastCommit list
+  execute_gather      <- executeCommands' walk (which instances run) and the gather of their
+                         commands for apply, with build_replies' executed mask and ret_first
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log         <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -837,6 +839,78 @@ class Engine:
         return _lib.MpxReplyBatch(p[0], n_sends, inst_base, n_inst, p[1], n_props, p[2], p[3],
                                   n_ret, p[4], kind, R.RB_GENERAL if general else 0,
                                   R.RB_NO_PAD if pad_client is None else pad_client, 0)
+
+    # ---- execute assembly: executeCommands' walk and the gather of its commands ----------------
+    def execute_gather(self, inst, committed_upto, executed, cmds, inst_base=0, ipg=None,
+                       sends=None, cap=None, pad=False, general=False, want_inst_first=True,
+                       want_grp_cmd_off=True):
+        """inst: INST_CMDS per window slot; committed_upto, executed: int32 per group (executed is
+        copied); cmds: (op, key, val) source arrays; sends: optional ACCEPT_SEND, for ret_first.
+        cap: None = what the call needs. Returns a dict: op, key, val (trimmed to what was
+        written), mask, executed, inst_first, ret_first, grp_cmd_off (None where not asked for) and
+        res (EXECUTE_RESULT scalar)."""
+        inst = _c(inst, R.INST_CMDS)
+        cu = _c(np.atleast_1d(committed_upto), np.int32)
+        ex = np.array(np.atleast_1d(executed), dtype=np.int32, copy=True)
+        op, key, val = _c(cmds[0], np.uint8), _c(cmds[1], np.int64), _c(cmds[2], np.int64)
+        sends = None if sends is None else _c(sends, R.ACCEPT_SEND)
+        n, G, n_src = len(inst), len(cu), len(op)
+        ipg = (n // G if G else 0) if ipg is None else ipg
+        if cap is None:
+            cap = int(inst["n_cmds"].astype(np.int64).sum())
+        o_op, o_key, o_val = (np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.int64),
+                              np.zeros(max(cap, 1), np.int64))
+        mask = np.zeros(max(n, 1), np.uint8)
+        ifirst = np.zeros(max(n, 1), np.uint64) if want_inst_first else None
+        rf = None if sends is None else np.zeros(max(len(sends), 1), np.uint64)
+        goff = np.zeros(G + 1, np.uint64) if want_grp_cmd_off else None
+        b = _lib.MpxExecuteBatch(_ptr(inst) if n else None, n, inst_base, ipg, G, _ptr(cu), _ptr(ex),
+                                 _ptr(ex), _ptr(op) if n_src else None,
+                                 _ptr(key) if n_src else None, _ptr(val) if n_src else None, n_src,
+                                 _ptr(sends), 0 if sends is None else len(sends),
+                                 (R.XG_PAD if pad else 0) | (R.XG_GENERAL if general else 0), 0)
+        out = _lib.MpxExecuteOut(_ptr(o_op) if cap else None, _ptr(o_key) if cap else None,
+                                 _ptr(o_val) if cap else None, cap, _ptr(mask), _ptr(ifirst),
+                                 _ptr(rf), _ptr(goff))
+        res = _lib.MpxExecuteResult()
+        rc = self.lib.mpx_execute_gather(self.h, C.byref(b), C.byref(out), C.byref(res))
+        self._check(rc, "mpx_execute_gather")
+        r = np.zeros((), R.EXECUTE_RESULT)
+        r["n_cmds"], r["n_inst"], r["n_groups"], r["reserved"] = (res.n_cmds, res.n_inst,
+                                                                  res.n_groups, res.reserved)
+        k = cap if pad else min(int(res.n_cmds), cap)
+        return dict(op=o_op[:k], key=o_key[:k], val=o_val[:k], mask=mask[:n], executed=ex,
+                    inst_first=None if ifirst is None else ifirst[:n],
+                    ret_first=None if rf is None else rf[:len(sends)], grp_cmd_off=goff, res=r)
+
+    def execute_gather_reserve(self, max_n_inst, max_n_groups):
+        self._check(self.lib.mpx_execute_gather_reserve(self.h, max_n_inst, max_n_groups),
+                    "mpx_execute_gather_reserve")
+
+    def execute_gather_dev(self, batch, out, d_res, stream=None):
+        """batch: _lib.MpxExecuteBatch, out: _lib.MpxExecuteOut, both of device pointers
+        (execute_batch_dev / execute_out_dev build them)"""
+        self._check(self.lib.mpx_execute_gather_dev(self.h, C.byref(batch), C.byref(out), d_res,
+                                                    stream), "mpx_execute_gather_dev")
+
+    @staticmethod
+    def execute_batch_dev(d_inst, n_inst, inst_base, ipg, n_groups, d_committed_upto, d_executed_in,
+                          d_executed_out, d_src_op, d_src_key, d_src_val, n_src, d_sends=None,
+                          n_sends=0, pad=False, general=False):
+        """the mpx_execute_batch of an execute_gather_dev call; every d_* is a device pointer or a
+        devbuf.DevArray"""
+        p = [getattr(x, "ptr", x) for x in (d_inst, d_committed_upto, d_executed_in, d_executed_out,
+                                            d_src_op, d_src_key, d_src_val, d_sends)]
+        return _lib.MpxExecuteBatch(p[0], n_inst, inst_base, ipg, n_groups, p[1], p[2], p[3], p[4],
+                                    p[5], p[6], n_src, p[7], n_sends,
+                                    (R.XG_PAD if pad else 0) | (R.XG_GENERAL if general else 0), 0)
+
+    @staticmethod
+    def execute_out_dev(d_op, d_key, d_val, cap, d_mask, d_inst_first=None, d_ret_first=None,
+                        d_grp_cmd_off=None):
+        p = [getattr(x, "ptr", x) for x in (d_op, d_key, d_val, d_mask, d_inst_first, d_ret_first,
+                                            d_grp_cmd_off)]
+        return _lib.MpxExecuteOut(p[0], p[1], p[2], cap, p[3], p[4], p[5], p[6])
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

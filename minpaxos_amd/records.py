@@ -163,6 +163,18 @@ REPLY_RESULT = np.dtype([("n_replies", "<u8"), ("n_slots", "<u8")])
 assert REPLY_RESULT.itemsize == 16
 
 
+# execute assembly (mpx_execute_gather): mpx_inst_cmds (where a window slot's Cmds live in the
+# source command arrays; flags 0 = Cmds == nil or a nil instance), the call flags, the one-launch
+# bounds and mpx_execute_result
+INST_CMDS = np.dtype([("first_cmd", "<u8"), ("n_cmds", "<u4"), ("flags", "<u4")])
+IC_HAS_CMDS = 1
+XG_PAD, XG_GENERAL = 1, 2
+XG_ONE_LAUNCH_INST, XG_ONE_LAUNCH_CMDS = 1024, 8192
+EXECUTE_RESULT = np.dtype([("n_cmds", "<u8"), ("n_inst", "<u8"), ("n_groups", "<u8"),
+                           ("reserved", "<u8")])
+assert INST_CMDS.itemsize == 16 and EXECUTE_RESULT.itemsize == 32
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds
