@@ -60,6 +60,10 @@
  *                            mpx_reply_recs mpx_encode_replies takes, and bcastCommit's send list
  *   mpx_execute_gather    <- executeCommands' walk (bareminpaxos.go:1066-1098 / paxos.go:675-706):
  *                            which instances run, and their commands gathered for mpx_apply
+ *   mpx_store_commands    <- where handleAccept, handleCommit and handlePropose assign an
+ *                            instance's Cmds (bareminpaxos.go:786-793, :861-868, :687-699): the
+ *                            commands appended to a device arena, the slots' mpx_inst_cmds written;
+ *                            mpx_store_compact squeezes the retired instances out of the arena
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -94,15 +98,17 @@
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
  *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
  *     and the encoders, mpx_unmarshal_frames_dev, mpx_decode_client_streams_dev,
- *     mpx_build_replies_dev and mpx_execute_gather_dev keep their offsets, maps and totals there:
+ *     mpx_build_replies_dev, mpx_execute_gather_dev, mpx_store_commands_dev and
+ *     mpx_store_compact_dev keep their offsets, maps and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
  *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
  *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve /
- *     mpx_build_replies_reserve / mpx_execute_gather_reserve, or a host-pointer mpx_apply /
+ *     mpx_build_replies_reserve / mpx_execute_gather_reserve / mpx_store_commands_reserve /
+ *     mpx_store_compact_reserve, or a host-pointer mpx_apply /
  *     mpx_replay_durable / mpx_unmarshal_frames / mpx_decode_client_streams / mpx_build_replies /
- *     mpx_execute_gather call that
+ *     mpx_execute_gather / mpx_store_commands / mpx_store_compact call that
  *     needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
@@ -128,7 +134,8 @@ extern "C" {
                               mpx_order_records[_reserve|_dev],
                               mpx_decode_client_streams[_reserve|_dev],
                               mpx_build_replies[_reserve|_dev],
-                              mpx_execute_gather[_reserve|_dev] */
+                              mpx_execute_gather[_reserve|_dev],
+                              mpx_store_commands[_reserve|_dev], mpx_store_compact[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1522,6 +1529,129 @@ int mpx_execute_gather_reserve(mpx_engine* eng, size_t max_n_inst, size_t max_n_
  * and mask any address; any other address is rejected with MPX_E_INVAL.                        */
 int mpx_execute_gather_dev(mpx_engine* eng, const mpx_execute_batch* b, const mpx_execute_out* out,
                            mpx_execute_result* d_res, void* stream);
+
+/* ---- store assembly: instance commands into a device command arena -----------------------------
+ * Where the Go assigns an instance's commands: MIN handleAccept's fresh Instance{..., accept.Command}
+ * (bareminpaxos.go:786-793) and CLASSIC's cmds = accept.Command (paxos.go:479-483, :491, :506),
+ * exactly the messages flagged MPX_AH_STORED; handleCommit's Instance{..., commit.Command} / Cmds =
+ * commit.Command (bareminpaxos.go:861-868 / paxos.go:526-534), flagged MPX_CH_CMDS; handlePropose's
+ * installed instance (bareminpaxos.go:687-699 / paxos.go:410-437), the slots flagged MPX_PH_ACCEPT
+ * or MPX_PH_PREPARE. handleCommitShort (bareminpaxos.go:890-898) assigns no commands: a record with
+ * value_id == MPX_VALUE_KEEP never stores. Unmarshal always makes a non-nil slice, so a stored
+ * message of zero commands leaves {first_cmd, 0, MPX_IC_HAS_CMDS}.
+ * mpx_store_commands appends the commands of the batch's storing items to an append-only arena
+ * (the source arrays mpx_execute_gather reads) and writes the instances' mpx_inst_cmds.
+ *   item -> commands   MSGS: item i is record p = perm ? perm[i] : i of the sources' concatenation;
+ *                      it belongs to source s with rec_base[s] <= p < rec_base[s + 1] (rec_base =
+ *                      the prefix sum of src[].n_recs) and its commands are [cmd_off[v],
+ *                      cmd_off[v + 1]) of that source, v = value_id. It stores when effect[i] &
+ *                      store_mask and value_id != MPX_VALUE_KEEP.
+ *                      SENDS: [first_cmd, first_cmd + n_cmds) of src[0]; an item stores when
+ *                      flags & (MPX_PH_ACCEPT | MPX_PH_PREPARE).
+ *   winner             of the storing items of one instance the last in array order wins (the
+ *                      handlers run per message in array order). Items are grouped by instance, so
+ *                      a storing item loses exactly when the next storing item names its instance.
+ *   effect             the winners' commands are appended at [*used, *used + n_cmds) in item order,
+ *                      inside an item in source order; inst[instance - inst_base] = {first_cmd,
+ *                      n_cmds, MPX_IC_HAS_CMDS} for every winner and no other slot is touched;
+ *                      *used advances by n_cmds. Work and scratch scale with n and the commands
+ *                      copied, never with n_inst.
+ *   all or nothing     *used + n_cmds > cap: nothing is written (arena, inst, *used), res is
+ *                      complete and carries MPX_SC_FULL, the call returns MPX_OK; the caller
+ *                      compacts or grows and repeats.
+ *   MPX_SC_GENERAL     takes the multi-launch path also for a call of at most
+ *                      MPX_SC_ONE_LAUNCH_ITEMS items whose sources hold at most
+ *                      MPX_SC_ONE_LAUNCH_CMDS commands in all, which otherwise runs as one kernel
+ *                      in one workgroup with no scratch; the bytes are the same.
+ * Errors, host form, answered before anything is staged: null required arrays, unknown kind or
+ * flags, reserved != 0, d_n given, n_src outside [1, MPX_SC_MAX_SRC] (SENDS: not 1), n_src > 1
+ * without perm, sum n_recs < n, a perm entry out of range, *used > cap, a storing item whose
+ * value_id >= n_frames of its source or whose command range leaves [0, n_cmds), a decreasing
+ * cmd_off -> MPX_E_INVAL; a storing item outside the window -> MPX_E_NIL_INSTANCE; n or the total
+ * at or above 2^32-1 -> MPX_E_UNSUPPORTED. Items that do not store are not judged.              */
+#define MPX_SC_MSGS 0u            /* kind: mpx_accept_msg records + slot-aligned effect bytes   */
+#define MPX_SC_SENDS 1u           /* kind: mpx_accept_send slots (ACCEPT | PREPARE store)       */
+#define MPX_SC_GENERAL 1u         /* call flag: force the multi-launch path                     */
+#define MPX_SC_FULL 1u            /* result flag: the arena could not take the batch            */
+#define MPX_SC_MAX_SRC 16         /* = MPX_ORDER_MAX_SRC                                        */
+#define MPX_SC_ONE_LAUNCH_ITEMS 1024
+#define MPX_SC_ONE_LAUNCH_CMDS 8192
+
+/* one connection's unmarshal output (MSGS), or the proposal arrays (SENDS: cmd_off null,
+ * n_frames 0, n_recs = n_sends) */
+typedef struct mpx_store_src {
+    const uint64_t* cmd_off;       /* n_frames + 1 entries                                       */
+    size_t n_frames;
+    const uint8_t* op;             /* the source's commands, n_cmds each                         */
+    const int64_t* key;
+    const int64_t* val;
+    size_t n_cmds;
+    size_t n_recs;                 /* records of this source in the concatenation perm indexes   */
+} mpx_store_src;
+
+typedef struct mpx_store_batch {
+    uint32_t kind, flags;          /* MPX_SC_MSGS / MPX_SC_SENDS; MPX_SC_GENERAL                 */
+    const void* items;             /* mpx_accept_msg[n] or mpx_accept_send[n]                    */
+    const uint8_t* effect;         /* MSGS: slot-aligned; SENDS: null                            */
+    size_t n;
+    const uint64_t* d_n;           /* optional, _dev only: min(*d_n, n) items are read, so the call
+                                      captures behind mpx_order_records_dev (&d_res->n)          */
+    const uint32_t* perm;          /* MSGS with n_src > 1: mpx_order_records' perm; else optional */
+    const mpx_store_src* src;
+    size_t n_src;
+    size_t n_inst;
+    int32_t inst_base;
+    uint32_t store_mask;           /* MSGS: MPX_AH_STORED and MPX_CH_CMDS are both 2             */
+    uint32_t reserved;             /* 0                                                          */
+} mpx_store_batch;
+
+typedef struct mpx_store_arena {
+    uint8_t* op;                   /* cap each                                                   */
+    int64_t* key;
+    int64_t* val;
+    size_t cap;
+    uint64_t* used;                /* in/out append cursor                                       */
+} mpx_store_arena;
+
+typedef struct mpx_store_result {
+    uint64_t n_stored;             /* slots written (winners)                                    */
+    uint64_t n_cmds;               /* their commands, complete also on MPX_SC_FULL               */
+    uint64_t n_superseded;         /* storing items that lost to a later one                     */
+    uint64_t flags;                /* MPX_SC_FULL                                                */
+} mpx_store_result;                /* 32 B */
+
+/* host form: stages only what the call writes (the appended range, the span of inst between the
+ * first and the last storing item, the cursor and res) */
+int mpx_store_commands(mpx_engine* eng, const mpx_store_batch* b, const mpx_store_arena* arena,
+                       mpx_inst_cmds* inst, mpx_store_result* res);
+/* scratch of mpx_store_commands_dev calls of up to max_n items (grows only; a larger reserve
+ * invalidates graphs captured before it) */
+int mpx_store_commands_reserve(mpx_engine* eng, size_t max_n);
+/* device form: b and arena are host structs of device pointers (b->src a host array of them). Needs
+ * mpx_store_commands_reserve first. Never allocates or synchronises, needs no memset on the stream;
+ * it captures into a graph. The per-item conditions above and *used > cap are reported through the
+ * error word (the code arrives at the next synchronising call): such an item neither stores nor
+ * supersedes, *used > cap is treated as MPX_SC_FULL, and every store stays inside its array.
+ * Alignment: items 16 bytes; cmd_off, key, val (sources and arena), used, d_n and d_res 8; d_inst
+ * 16; perm 4; op bytes and effect any address; any other address is rejected with MPX_E_INVAL. */
+int mpx_store_commands_dev(mpx_engine* eng, const mpx_store_batch* b, const mpx_store_arena* arena,
+                           mpx_inst_cmds* d_inst, mpx_store_result* d_res, void* stream);
+
+/* Compaction, out of place: every slot of inst[n_inst] with MPX_IC_HAS_CMDS, in window order, has
+ * its commands copied from `from` to `to` from position 0, and its first_cmd rewritten in place;
+ * to->used is written (not read), `from` is left as it was. Slots without the flag are untouched:
+ * an instance is retired by clearing its flag first. A total above to->cap: nothing is written and
+ * res carries MPX_SC_FULL. res: n_stored = the flagged slots, n_cmds = their commands,
+ * n_superseded = 0. A flagged slot whose range leaves [0, *from->used) -> MPX_E_INVAL (host form);
+ * the _dev form raises the error word and the slot is left {its new position, 0 commands}. from
+ * and to must not overlap (checked by address range), *from->used <= from->cap; n_inst or the
+ * total at or above 2^32-1 -> MPX_E_UNSUPPORTED. Alignment as above.                           */
+int mpx_store_compact(mpx_engine* eng, mpx_inst_cmds* inst, size_t n_inst,
+                      const mpx_store_arena* from, const mpx_store_arena* to, mpx_store_result* res);
+int mpx_store_compact_reserve(mpx_engine* eng, size_t max_n_inst);
+int mpx_store_compact_dev(mpx_engine* eng, mpx_inst_cmds* d_inst, size_t n_inst,
+                          const mpx_store_arena* from, const mpx_store_arena* to,
+                          mpx_store_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

@@ -108,6 +108,27 @@ class MpxExecuteResult(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class MpxStoreSrc(C.Structure):
+    _fields_ = [("cmd_off", _p), ("n_frames", _sz), ("op", _p), ("key", _p), ("val", _p),
+                ("n_cmds", _sz), ("n_recs", _sz)]
+
+
+class MpxStoreBatch(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("items", _p), ("effect", _p),
+                ("n", _sz), ("d_n", _p), ("perm", _p), ("src", C.POINTER(MpxStoreSrc)),
+                ("n_src", _sz), ("n_inst", _sz), ("inst_base", C.c_int32),
+                ("store_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MpxStoreArena(C.Structure):
+    _fields_ = [("op", _p), ("key", _p), ("val", _p), ("cap", _sz), ("used", _p)]
+
+
+class MpxStoreResult(C.Structure):
+    _fields_ = [("n_stored", C.c_uint64), ("n_cmds", C.c_uint64), ("n_superseded", C.c_uint64),
+                ("flags", C.c_uint64)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -197,6 +218,16 @@ SIGNATURES = {
     "mpx_execute_gather_reserve": (C.c_int, [_p, _sz, _sz]),
     "mpx_execute_gather_dev": (C.c_int, [_p, C.POINTER(MpxExecuteBatch),
                                          C.POINTER(MpxExecuteOut), _p, _p]),
+    "mpx_store_commands": (C.c_int, [_p, C.POINTER(MpxStoreBatch), C.POINTER(MpxStoreArena), _p,
+                                     C.POINTER(MpxStoreResult)]),
+    "mpx_store_commands_reserve": (C.c_int, [_p, _sz]),
+    "mpx_store_commands_dev": (C.c_int, [_p, C.POINTER(MpxStoreBatch), C.POINTER(MpxStoreArena),
+                                         _p, _p, _p]),
+    "mpx_store_compact": (C.c_int, [_p, _p, _sz, C.POINTER(MpxStoreArena),
+                                    C.POINTER(MpxStoreArena), C.POINTER(MpxStoreResult)]),
+    "mpx_store_compact_reserve": (C.c_int, [_p, _sz]),
+    "mpx_store_compact_dev": (C.c_int, [_p, _p, _sz, C.POINTER(MpxStoreArena),
+                                        C.POINTER(MpxStoreArena), _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

@@ -309,6 +309,26 @@ hipError_t launch_execute_gather(const mpx_execute_batch* b, const mpx_execute_o
                                  mpx_execute_result* res, void* work, uint64_t work_bytes,
                                  uint64_t group_cap, uint32_t* err, hipStream_t stream);
 
+// ---- store assembly (mpx_store_commands, mpx_store_compact; store.hip) -------------------------
+// Scratch of a general-path call of n items (store) or n window slots (compaction): the call's
+// words, the items' lengths and source positions, the storing items' list, the winners' lengths
+// and scanned offsets, the workgroups' winner counts and the scans' tile totals. No control words:
+// nothing in it lives between calls; monotone in n.
+uint64_t store_work_bytes(uint64_t n, Carver&& c = Carver());
+// b, arena: host structs of device pointers (validated by the caller: kind, flags, the kind's
+// arrays, n below 2^32-1, n_src in [1, MPX_SC_MAX_SRC], sum n_recs >= n). One kernel in one
+// workgroup with no scratch when n <= MPX_SC_ONE_LAUNCH_ITEMS, the sources hold at most
+// MPX_SC_ONE_LAUNCH_CMDS commands and MPX_SC_GENERAL is not set, or when n == 0. Nothing is
+// written outside [*used, cap) of the arena or outside inst[0 .. n_inst).
+hipError_t launch_store_commands(const mpx_store_batch* b, const mpx_store_arena* arena,
+                                 mpx_inst_cmds* inst, mpx_store_result* res, void* work,
+                                 uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+// from, to: host structs of device pointers that do not overlap. A call with n_inst == 0 uses no
+// scratch.
+hipError_t launch_store_compact(mpx_inst_cmds* inst, uint64_t n_inst, const mpx_store_arena* from,
+                                const mpx_store_arena* to, mpx_store_result* res, void* work,
+                                uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

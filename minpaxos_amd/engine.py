@@ -29,6 +29,9 @@ Names and argument meaning follow the reference handlers they replace:
                          and CLASSIC's bcastCommit list
   execute_gather      <- executeCommands' walk (which instances run) and the gather of their
                          commands for apply, with build_replies' executed mask and ret_first
+  store_commands      <- where handleAccept / handleCommit / handlePropose assign an instance's
+                         Cmds: the batch's commands appended to a command arena, the slots'
+                         INST_CMDS written; store_compact squeezes retired instances out of it
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log         <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -911,6 +914,122 @@ class Engine:
         p = [getattr(x, "ptr", x) for x in (d_op, d_key, d_val, d_mask, d_inst_first, d_ret_first,
                                             d_grp_cmd_off)]
         return _lib.MpxExecuteOut(p[0], p[1], p[2], cap, p[3], p[4], p[5], p[6])
+
+    # ---- store assembly: instance commands into a command arena, and its compaction ------------
+    @staticmethod
+    def _store_srcs(sources, ptr_of):
+        """the mpx_store_src array of sources = [dict(cmd_off=, op=, key=, val=, n_recs=)];
+        returns (ctypes array, what must stay alive)"""
+        arr = (_lib.MpxStoreSrc * max(len(sources), 1))()
+        keep = []
+        for s, x in enumerate(sources):
+            off = x.get("cmd_off")
+            n_cmds = x["n_cmds"] if "n_cmds" in x else len(x["op"])
+            n_frames = x["n_frames"] if "n_frames" in x else (0 if off is None else len(off) - 1)
+            p = [ptr_of(x.get(k), keep, t) for k, t in (("cmd_off", np.uint64), ("op", np.uint8),
+                                                        ("key", np.int64), ("val", np.int64))]
+            arr[s] = _lib.MpxStoreSrc(p[0], n_frames, p[1], p[2], p[3], n_cmds, x["n_recs"])
+        return arr, keep
+
+    def store_commands(self, kind, items, sources, arena, used, inst, inst_base=0, effect=None,
+                       perm=None, store_mask=R.AH_STORED, general=False):
+        """kind: R.SC_MSGS (items ACCEPT_MSG, effect uint8 per item) or R.SC_SENDS (items
+        ACCEPT_SEND); sources: a list of dicts cmd_off / op / key / val / n_recs (SENDS: the
+        proposal arrays, cmd_off None); arena: (op, key, val) arrays of one capacity, appended to IN
+        PLACE from `used`; inst: INST_CMDS window, written IN PLACE. Returns (used after the call,
+        result STORE_RESULT scalar)."""
+        items = _c(items, R.ACCEPT_SEND if kind == R.SC_SENDS else R.ACCEPT_MSG)
+        effect = None if effect is None else _c(effect, np.uint8)
+        perm = None if perm is None else _c(perm, np.uint32)
+        a_op, a_key, a_val = arena
+        assert a_op.dtype == np.uint8 and a_key.dtype == np.int64 and a_val.dtype == np.int64
+        assert inst.dtype == R.INST_CMDS and inst.flags.c_contiguous
+
+        def ptr_of(x, keep, t):
+            if x is None or not len(x):
+                return None
+            keep.append(_c(x, t))
+            return _ptr(keep[-1])
+        src, keep = self._store_srcs(sources, ptr_of)
+        cur = np.array([used], np.uint64)
+        n, cap = len(items), len(a_op)
+        b = _lib.MpxStoreBatch(kind, R.SC_GENERAL if general else 0, _ptr(items) if n else None,
+                               _ptr(effect), n, None, _ptr(perm), src, len(sources), len(inst),
+                               inst_base, store_mask, 0)
+        ar = _lib.MpxStoreArena(_ptr(a_op) if cap else None, _ptr(a_key) if cap else None,
+                                _ptr(a_val) if cap else None, cap, _ptr(cur))
+        res = _lib.MpxStoreResult()
+        rc = self.lib.mpx_store_commands(self.h, C.byref(b), C.byref(ar),
+                                         _ptr(inst) if len(inst) else None, C.byref(res))
+        self._check(rc, "mpx_store_commands")
+        del keep
+        return int(cur[0]), self._store_result(res)
+
+    @staticmethod
+    def _store_result(res):
+        r = np.zeros((), R.STORE_RESULT)
+        for f in R.STORE_RESULT.names:
+            r[f] = getattr(res, f)
+        return r
+
+    def store_commands_reserve(self, max_n):
+        self._check(self.lib.mpx_store_commands_reserve(self.h, max_n), "mpx_store_commands_reserve")
+
+    def store_commands_dev(self, batch, arena, d_inst, d_res, stream=None):
+        """batch: _lib.MpxStoreBatch, arena: _lib.MpxStoreArena, both of device pointers
+        (store_batch_dev / store_arena_dev build them)"""
+        self._check(self.lib.mpx_store_commands_dev(self.h, C.byref(batch), C.byref(arena),
+                                                    getattr(d_inst, "ptr", d_inst),
+                                                    getattr(d_res, "ptr", d_res), stream),
+                    "mpx_store_commands_dev")
+
+    @staticmethod
+    def store_batch_dev(kind, d_items, n, sources, n_inst, inst_base=0, d_effect=None, d_perm=None,
+                        d_n=None, store_mask=R.AH_STORED, general=False):
+        """the mpx_store_batch of a store_commands_dev call; sources: a list of dicts of device
+        pointers (or devbuf.DevArrays) cmd_off / op / key / val with n_frames, n_cmds, n_recs. The
+        batch keeps its source array alive."""
+        def ptr_of(x, keep, t):
+            return getattr(x, "ptr", x)
+        src, _ = Engine._store_srcs(sources, ptr_of)
+        p = [getattr(x, "ptr", x) for x in (d_items, d_effect, d_n, d_perm)]
+        b = _lib.MpxStoreBatch(kind, R.SC_GENERAL if general else 0, p[0], p[1], n, p[2], p[3], src,
+                               len(sources), n_inst, inst_base, store_mask, 0)
+        b._src_keep = src
+        return b
+
+    @staticmethod
+    def store_arena_dev(d_op, d_key, d_val, cap, d_used):
+        p = [getattr(x, "ptr", x) for x in (d_op, d_key, d_val, d_used)]
+        return _lib.MpxStoreArena(p[0], p[1], p[2], cap, p[3])
+
+    def store_compact(self, inst, src_arena, used, dst_arena):
+        """inst: INST_CMDS window, rewritten IN PLACE; src_arena / dst_arena: (op, key, val) arrays;
+        used: the source arena's cursor. Returns (the target's cursor, result STORE_RESULT)."""
+        assert inst.dtype == R.INST_CMDS and inst.flags.c_contiguous
+        f_used, t_used = np.array([used], np.uint64), np.zeros(1, np.uint64)
+
+        def arena(a, cur):
+            cap = len(a[0])
+            assert a[0].dtype == np.uint8 and a[1].dtype == np.int64 and a[2].dtype == np.int64
+            return _lib.MpxStoreArena(_ptr(a[0]) if cap else None, _ptr(a[1]) if cap else None,
+                                      _ptr(a[2]) if cap else None, cap, _ptr(cur))
+        f, t = arena(src_arena, f_used), arena(dst_arena, t_used)
+        res = _lib.MpxStoreResult()
+        rc = self.lib.mpx_store_compact(self.h, _ptr(inst) if len(inst) else None, len(inst),
+                                        C.byref(f), C.byref(t), C.byref(res))
+        self._check(rc, "mpx_store_compact")
+        return int(t_used[0]), self._store_result(res)
+
+    def store_compact_reserve(self, max_n_inst):
+        self._check(self.lib.mpx_store_compact_reserve(self.h, max_n_inst), "mpx_store_compact_reserve")
+
+    def store_compact_dev(self, d_inst, n_inst, src_arena, dst_arena, d_res, stream=None):
+        """src_arena, dst_arena: _lib.MpxStoreArena of device pointers (store_arena_dev)"""
+        self._check(self.lib.mpx_store_compact_dev(self.h, getattr(d_inst, "ptr", d_inst), n_inst,
+                                                   C.byref(src_arena), C.byref(dst_arena),
+                                                   getattr(d_res, "ptr", d_res), stream),
+                    "mpx_store_compact_dev")
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

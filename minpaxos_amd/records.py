@@ -175,6 +175,20 @@ EXECUTE_RESULT = np.dtype([("n_cmds", "<u8"), ("n_inst", "<u8"), ("n_groups", "<
 assert INST_CMDS.itemsize == 16 and EXECUTE_RESULT.itemsize == 32
 
 
+# store assembly (mpx_store_commands / mpx_store_compact): the kinds, the call flag, the result
+# flag, the one-launch bounds, mpx_store_result and the host layout of mpx_store_src
+SC_MSGS, SC_SENDS = 0, 1
+SC_GENERAL = 1
+SC_FULL = 1
+SC_MAX_SRC = 16
+SC_ONE_LAUNCH_ITEMS, SC_ONE_LAUNCH_CMDS = 1024, 8192
+STORE_RESULT = np.dtype([("n_stored", "<u8"), ("n_cmds", "<u8"), ("n_superseded", "<u8"),
+                         ("flags", "<u8")])
+STORE_SRC = np.dtype([("cmd_off", "<u8"), ("n_frames", "<u8"), ("op", "<u8"), ("key", "<u8"),
+                      ("val", "<u8"), ("n_cmds", "<u8"), ("n_recs", "<u8")])
+assert STORE_RESULT.itemsize == 32 and STORE_SRC.itemsize == 56
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds
