@@ -64,6 +64,11 @@
  *                            instance's Cmds (bareminpaxos.go:786-793, :861-868, :687-699): the
  *                            commands appended to a device arena, the slots' mpx_inst_cmds written;
  *                            mpx_store_compact squeezes the retired instances out of the arena
+ *   mpx_record_log        <- the handlers' stable-store appends: recordInstanceMetadata (+
+ *                            recordCommands) of handlePropose, handleAccept, handleCommit[Short]
+ *                            and handleAcceptReply's commit branch (bareminpaxos.go:697-699,
+ *                            :798-800, :881-882, :909, :1045-1046 / paxos.go:436-438, :547-548,
+ *                            :574, :656-657): a batch's durable-log bytes as one run
  *   mpx_encode_log        <- minpaxosproto.(*Instance).Marshal (minpaxosprotomarsh.go:100-124) for
  *                            the CatchUpLog of bcastAccept (bareminpaxos.go:488-513), and
  *                            recordInstanceMetadata + recordCommands (bareminpaxos.go:164-188)
@@ -98,17 +103,17 @@
  *     control words or scratch in the handle between calls (tickets, maxima, the replica-batch
  *     list tags, the replay's binned-maximum scratch), each reset by the call's last workgroup,
  *     and the encoders, mpx_unmarshal_frames_dev, mpx_decode_client_streams_dev,
- *     mpx_build_replies_dev, mpx_execute_gather_dev, mpx_store_commands_dev and
- *     mpx_store_compact_dev keep their offsets, maps and totals there:
+ *     mpx_build_replies_dev, mpx_execute_gather_dev, mpx_store_commands_dev,
+ *     mpx_store_compact_dev and mpx_record_log_dev keep their offsets, maps and totals there:
  *     all *_dev calls on one handle must be issued in ONE stream order (one stream, or streams
  *     ordered by events) — two such calls in flight at once corrupt every later call.
  *   - a captured graph keeps the scratch pointers of the calls it captured: growing a handle's
  *     scratch afterwards (a larger mpx_apply_reserve / mpx_replay_durable_reserve /
  *     mpx_unmarshal_frames_reserve / mpx_decode_client_streams_reserve /
  *     mpx_build_replies_reserve / mpx_execute_gather_reserve / mpx_store_commands_reserve /
- *     mpx_store_compact_reserve, or a host-pointer mpx_apply /
+ *     mpx_store_compact_reserve / mpx_record_log_reserve, or a host-pointer mpx_apply /
  *     mpx_replay_durable / mpx_unmarshal_frames / mpx_decode_client_streams / mpx_build_replies /
- *     mpx_execute_gather / mpx_store_commands / mpx_store_compact call that
+ *     mpx_execute_gather / mpx_store_commands / mpx_store_compact / mpx_record_log call that
  *     needs more) frees the old buffers and
  *     invalidates such graphs; reserve the largest size before capturing.
  *   - where the reference would panic (nil instance, peer id outside peerCommits), the engine
@@ -135,7 +140,8 @@ extern "C" {
                               mpx_decode_client_streams[_reserve|_dev],
                               mpx_build_replies[_reserve|_dev],
                               mpx_execute_gather[_reserve|_dev],
-                              mpx_store_commands[_reserve|_dev], mpx_store_compact[_reserve|_dev] */
+                              mpx_store_commands[_reserve|_dev], mpx_store_compact[_reserve|_dev],
+                              mpx_record_log[_reserve|_dev], mpx_record_bound */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1652,6 +1658,114 @@ int mpx_store_compact_reserve(mpx_engine* eng, size_t max_n_inst);
 int mpx_store_compact_dev(mpx_engine* eng, mpx_inst_cmds* d_inst, size_t n_inst,
                           const mpx_store_arena* from, const mpx_store_arena* to,
                           mpx_store_result* d_res, void* stream);
+
+/* ---- record assembly: a batch's durable-log bytes built on the device ---------------------------
+ * Every handler of the reference ends in a write to the stable store: recordInstanceMetadata and,
+ * where the message carries commands, recordCommands (bareminpaxos.go:164-188 / paxos.go:107-130).
+ * mpx_record_log walks the batch's items in array order and appends, for every RECORDING item, the
+ * bytes its handler writes, back to back, into out: the batch's stable-store append as one byte
+ * run (the host keeps Write + Sync).
+ *   kind            items                      records when                  metadata
+ *   MPX_LR_ACCEPTS  mpx_accept_msg + effect    effect[i] & MPX_AH_STORED     {ballot, ACCEPTED, instance}
+ *                   handleAccept, bareminpaxos.go:798-800. Commands: the message's, resolved as
+ *                   mpx_store_commands MSGS resolves them (perm, up to MPX_SC_MAX_SRC sources,
+ *                   cmd_off[value_id] ..). EVERY storing message records, not only the instance's
+ *                   winner (a value_id of MPX_VALUE_KEEP is judged like any other handle).
+ *   MPX_LR_COMMITS  mpx_accept_msg + effect    every item                    {ballot, COMMITTED, instance}
+ *                   handleCommit / handleCommitShort, bareminpaxos.go:881-882, :909 / paxos.go:
+ *                   547-548, :574. Commands where effect[i] & MPX_CH_CMDS and value_id !=
+ *                   MPX_VALUE_KEEP, resolved as above; a CommitShort writes metadata only.
+ *   MPX_LR_SENDS    mpx_accept_send            flags & MPX_PH_ACCEPT         {ballot, PREPARED, instance}
+ *                   handlePropose, bareminpaxos.go:697-698 / paxos.go:436-437. Commands:
+ *                   [first_cmd, first_cmd + n_cmds) of src[0]. MPX_PH_PREPARE stores but records
+ *                   nothing (paxos.go:421-428); NOT_LEADER and REFUSED slots record nothing.
+ *   MPX_LR_DECIDED  mpx_accept_send + mask     flags & MPX_PH_ACCEPT and     {ballot, COMMITTED, instance}
+ *                                              mask[instance - inst_base]
+ *                   handleAcceptReply's commit branch, bareminpaxos.go:1045 / paxos.go:656: the
+ *                   ballot mpx_build_replies' mpx_commit_send takes from the same slot. No
+ *                   commands; src is not read (n_src 0 .. MPX_SC_MAX_SRC).
+ *   format          MPX_LOG_DURABLE: MIN's 12-byte metadata (Ballot, Status, instNo as LE u32).
+ *                   MPX_LOG_DURABLE_CLASSIC: paxos.go:107-116, Ballot LE u32 and one status byte, 5
+ *                   bytes, no instance number. Commands are 17 bytes each (Op, K, V) in both. The
+ *                   format is a field of the call, independent of mpx_config.mode.
+ *                   mpx_encode_log does not take MPX_LOG_DURABLE_CLASSIC.
+ *                   MPX_LR_ACCEPTS with MPX_LOG_DURABLE_CLASSIC -> MPX_E_UNSUPPORTED: CLASSIC's
+ *                   handleAccept records the instance's status at that message, which is COMMITTED
+ *                   in the reordered-ACCEPT branch (paxos.go:506-509, :514); neither effect nor the
+ *                   final state tells it.
+ *   order           records come out in array order: the handlers' contract order, grouped by
+ *                   instance, arrival order kept inside an instance. (The reference appends in
+ *                   arrival order across instances too; replay keeps the last record of an
+ *                   instance, so it sees no difference.)
+ *   outputs         out[out_cap]; item_off[n + 1] (optional): where item i's record starts, a
+ *                   non-recording item has zero length, item_off[n] = n_bytes, entries past the
+ *                   items read (d_n) equal the total; always written. res: always complete.
+ *   all or nothing  n_bytes > out_cap: out is left untouched, res carries MPX_LR_FULL, the call
+ *                   returns MPX_OK. mpx_record_bound(n, m) = 12 n + 17 m bounds both formats.
+ *   MPX_LR_GENERAL  takes the multi-launch path also for a call of at most
+ *                   MPX_LR_ONE_LAUNCH_ITEMS items whose sources hold at most
+ *                   MPX_LR_ONE_LAUNCH_CMDS commands in all, which otherwise runs as one kernel in
+ *                   one workgroup with no scratch; the bytes are the same. Work and scratch scale
+ *                   with n and the bytes written, never with n_inst.
+ * Errors, host form, answered before anything is staged: null required arrays (res; items with n;
+ * effect for ACCEPTS / COMMITS; mask for DECIDED with n_inst; src except for DECIDED; out with
+ * out_cap; a source's arrays), unknown kind, format or flags, reserved != 0, d_n given, n_src
+ * outside [1, MPX_SC_MAX_SRC] (SENDS: not 1; DECIDED: above MPX_SC_MAX_SRC), n_src > 1 without
+ * perm, sum n_recs < n (not DECIDED), a perm entry out of range, a recording item whose value_id >=
+ * n_frames of its source or whose command range leaves [0, n_cmds), a decreasing cmd_off ->
+ * MPX_E_INVAL; MPX_LR_DECIDED with a slot flagged MPX_PH_ACCEPT whose instance lies outside the
+ * window -> MPX_E_NIL_INSTANCE; n or the byte total at or above 2^32-1 -> MPX_E_UNSUPPORTED. Items
+ * that do not record are not judged.                                                          */
+#define MPX_LOG_DURABLE_CLASSIC 2 /* mpx_record_batch.format only                               */
+#define MPX_LR_ACCEPTS 0u
+#define MPX_LR_COMMITS 1u
+#define MPX_LR_SENDS 2u
+#define MPX_LR_DECIDED 3u
+#define MPX_LR_GENERAL 1u         /* call flag: force the multi-launch path                     */
+#define MPX_LR_FULL 1u            /* result flag: out could not take the run                    */
+#define MPX_LR_ONE_LAUNCH_ITEMS 1024
+#define MPX_LR_ONE_LAUNCH_CMDS 8192
+
+typedef struct mpx_record_batch {
+    uint32_t kind, flags;          /* MPX_LR_*; MPX_LR_GENERAL                                   */
+    uint32_t format, reserved;     /* MPX_LOG_DURABLE / MPX_LOG_DURABLE_CLASSIC; 0               */
+    const void* items;             /* mpx_accept_msg[n] or mpx_accept_send[n]                    */
+    const uint8_t* effect;         /* ACCEPTS, COMMITS: slot-aligned; else null                  */
+    const uint8_t* mask;           /* DECIDED: mask[n_inst]; else null                           */
+    size_t n;
+    const uint64_t* d_n;           /* optional, _dev only: min(*d_n, n) items are read, so the call
+                                      captures behind mpx_order_records_dev (&d_res->n)          */
+    const uint32_t* perm;          /* ACCEPTS / COMMITS with n_src > 1: mpx_order_records' perm  */
+    const mpx_store_src* src;      /* as mpx_store_batch.src                                     */
+    size_t n_src;
+    size_t n_inst;                 /* DECIDED: the window of mask                                */
+    int32_t inst_base;
+    uint32_t pad;                  /* not read                                                   */
+} mpx_record_batch;
+
+typedef struct mpx_record_result {
+    uint64_t n_recs;               /* recording items                                            */
+    uint64_t n_cmds;               /* their commands                                             */
+    uint64_t n_bytes;              /* the run, complete also on MPX_LR_FULL                      */
+    uint64_t flags;                /* MPX_LR_FULL                                                */
+} mpx_record_result;               /* 32 B */
+
+/* 12 n + 17 m: the most bytes n items carrying m commands in all can record, either format */
+size_t mpx_record_bound(size_t n, size_t m);
+int mpx_record_log(mpx_engine* eng, const mpx_record_batch* b, uint8_t* out, size_t out_cap,
+                   uint64_t* item_off, mpx_record_result* res);
+/* scratch of mpx_record_log_dev calls of up to max_n items (grows only; a larger reserve
+ * invalidates graphs captured before it) */
+int mpx_record_log_reserve(mpx_engine* eng, size_t max_n);
+/* device form: b is a host struct of device pointers (b->src a host array of them). Needs
+ * mpx_record_log_reserve first. Never allocates or synchronises, needs no memset on the stream;
+ * it captures into a graph. The per-item conditions above are reported through the error word
+ * (the code arrives at the next synchronising call): such an item records nothing, and every
+ * store stays inside its array. Alignment: items 16 bytes; cmd_off, key, val, d_item_off, d_n and
+ * d_res 8; perm 4; op, effect, mask and d_out any address; any other address is rejected with
+ * MPX_E_INVAL.                                                                                 */
+int mpx_record_log_dev(mpx_engine* eng, const mpx_record_batch* b, uint8_t* d_out, size_t out_cap,
+                       uint64_t* d_item_off, mpx_record_result* d_res, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

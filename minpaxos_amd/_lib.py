@@ -129,6 +129,18 @@ class MpxStoreResult(C.Structure):
                 ("flags", C.c_uint64)]
 
 
+class MpxRecordBatch(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("format", C.c_uint32),
+                ("reserved", C.c_uint32), ("items", _p), ("effect", _p), ("mask", _p), ("n", _sz),
+                ("d_n", _p), ("perm", _p), ("src", C.POINTER(MpxStoreSrc)), ("n_src", _sz),
+                ("n_inst", _sz), ("inst_base", C.c_int32), ("pad", C.c_uint32)]
+
+
+class MpxRecordResult(C.Structure):
+    _fields_ = [("n_recs", C.c_uint64), ("n_cmds", C.c_uint64), ("n_bytes", C.c_uint64),
+                ("flags", C.c_uint64)]
+
+
 class MpxApplyIo(C.Structure):
     _fields_ = [("op", _p), ("key", _p), ("val", _p), ("ret", _p), ("conf", _p),
                 ("cap", C.c_uint64)]
@@ -228,6 +240,11 @@ SIGNATURES = {
     "mpx_store_compact_reserve": (C.c_int, [_p, _sz]),
     "mpx_store_compact_dev": (C.c_int, [_p, _p, _sz, C.POINTER(MpxStoreArena),
                                         C.POINTER(MpxStoreArena), _p, _p]),
+    "mpx_record_bound": (_sz, [_sz, _sz]),
+    "mpx_record_log": (C.c_int, [_p, C.POINTER(MpxRecordBatch), _p, _sz, _p,
+                                 C.POINTER(MpxRecordResult)]),
+    "mpx_record_log_reserve": (C.c_int, [_p, _sz]),
+    "mpx_record_log_dev": (C.c_int, [_p, C.POINTER(MpxRecordBatch), _p, _sz, _p, _p, _p]),
     "mpx_encode_log_bound": (_sz, [_sz, _sz]),
     "mpx_encode_log": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p, _p, _sz, _p, _sz, _p]),
     "mpx_encode_log_reserve": (C.c_int, [_p, _sz, _sz]),

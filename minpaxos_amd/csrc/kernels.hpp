@@ -329,6 +329,20 @@ hipError_t launch_store_compact(mpx_inst_cmds* inst, uint64_t n_inst, const mpx_
                                 const mpx_store_arena* to, mpx_store_result* res, void* work,
                                 uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- record assembly (mpx_record_log; record.hip) ---------------------------------------------
+// Scratch of a general-path call of n items: the items' sizes / scanned offsets and source
+// positions, the workgroups' record counts and the scan's tile totals. No control words: nothing
+// in it lives between calls; monotone in n.
+uint64_t record_work_bytes(uint64_t n, Carver&& c = Carver());
+// b: a host struct of device pointers (validated by the caller: kind, format, flags, the kind's
+// arrays, n below 2^32-1, n_src at most MPX_SC_MAX_SRC, sum n_recs >= n). One kernel in one
+// workgroup with no scratch when n <= MPX_LR_ONE_LAUNCH_ITEMS, the sources hold at most
+// MPX_LR_ONE_LAUNCH_CMDS commands and MPX_LR_GENERAL is not set, or when n == 0. Nothing is
+// written outside out[0 .. out_cap) and item_off[0 .. n].
+hipError_t launch_record_log(const mpx_record_batch* b, uint8_t* out, uint64_t out_cap, uint64_t* item_off,
+                             mpx_record_result* res, void* work, uint64_t work_bytes, uint32_t* err,
+                             hipStream_t stream);
+
 // ---- instance-log encoding (mpx_encode_log) ----------------------------------------------
 uint64_t logenc_work_bytes(uint64_t n, uint64_t m, Carver&& c = Carver());
 uint64_t logenc_max_bytes(uint64_t n, uint64_t m);

@@ -32,6 +32,8 @@ Names and argument meaning follow the reference handlers they replace:
   store_commands      <- where handleAccept / handleCommit / handlePropose assign an instance's
                          Cmds: the batch's commands appended to a command arena, the slots'
                          INST_CMDS written; store_compact squeezes retired instances out of it
+  record_log          <- the handlers' recordInstanceMetadata (+ recordCommands): a batch's durable-log
+                         bytes as one run, MIN's 12-byte or CLASSIC's 5-byte metadata
   replay_durable      <- getDataFromStableStore (bareminpaxos.go:122-161)
   encode_log         <- Instance.Marshal (bcastAccept's CatchUpLog) / recordInstanceMetadata +
                          recordCommands (the durable log)
@@ -1030,6 +1032,76 @@ class Engine:
                                                    C.byref(src_arena), C.byref(dst_arena),
                                                    getattr(d_res, "ptr", d_res), stream),
                     "mpx_store_compact_dev")
+
+    # ---- record assembly: a batch's durable-log bytes ---------------------------------------------
+    def record_log(self, kind, fmt, items, sources=(), effect=None, perm=None, mask=None,
+                   inst_base=0, out_cap=None, general=False, want_item_off=True):
+        """kind: R.LR_ACCEPTS / R.LR_COMMITS (items ACCEPT_MSG, effect uint8 per item), R.LR_SENDS or
+        R.LR_DECIDED (items ACCEPT_SEND; DECIDED: mask uint8 per window slot from inst_base); fmt:
+        R.LOG_DURABLE / R.LOG_DURABLE_CLASSIC; sources as store_commands takes them. out_cap: the
+        output's capacity (default: the bound of the call's sizes). Returns (the run's bytes, empty
+        when it did not fit; item_off u64[n + 1] or None; result RECORD_RESULT scalar)."""
+        items = _c(items, R.ACCEPT_MSG if kind in (R.LR_ACCEPTS, R.LR_COMMITS) else R.ACCEPT_SEND)
+        effect = None if effect is None else _c(effect, np.uint8)
+        perm = None if perm is None else _c(perm, np.uint32)
+        mask = None if mask is None else _c(mask, np.uint8)
+
+        def ptr_of(x, keep, t):
+            if x is None or not len(x):
+                return None
+            keep.append(_c(x, t))
+            return _ptr(keep[-1])
+        src, keep = self._store_srcs(sources, ptr_of)
+        n = len(items)
+        if out_cap is None:
+            out_cap = R.record_bound(n, sum(x["n_cmds"] if "n_cmds" in x else len(x["op"])
+                                            for x in sources))
+        out = np.zeros(out_cap, np.uint8)
+        item_off = np.zeros(n + 1, np.uint64) if want_item_off else None
+        b = _lib.MpxRecordBatch(kind, R.LR_GENERAL if general else 0, fmt, 0,
+                                _ptr(items) if n else None, _ptr(effect), _ptr(mask), n, None,
+                                _ptr(perm), src if len(sources) else None, len(sources),
+                                0 if mask is None else len(mask), inst_base, 0)
+        res = _lib.MpxRecordResult()
+        rc = self.lib.mpx_record_log(self.h, C.byref(b), _ptr(out) if out_cap else None, out_cap,
+                                     _ptr(item_off), C.byref(res))
+        self._check(rc, "mpx_record_log")
+        del keep
+        r = self._record_result(res)
+        return out[:0 if int(r["flags"]) & R.LR_FULL else int(r["n_bytes"])], item_off, r
+
+    @staticmethod
+    def _record_result(res):
+        r = np.zeros((), R.RECORD_RESULT)
+        for f in R.RECORD_RESULT.names:
+            r[f] = getattr(res, f)
+        return r
+
+    def record_log_reserve(self, max_n):
+        self._check(self.lib.mpx_record_log_reserve(self.h, max_n), "mpx_record_log_reserve")
+
+    def record_log_dev(self, batch, d_out, out_cap, d_item_off, d_res, stream=None):
+        """batch: _lib.MpxRecordBatch of device pointers (record_batch_dev builds it)"""
+        self._check(self.lib.mpx_record_log_dev(self.h, C.byref(batch), getattr(d_out, "ptr", d_out),
+                                                out_cap, getattr(d_item_off, "ptr", d_item_off),
+                                                getattr(d_res, "ptr", d_res), stream),
+                    "mpx_record_log_dev")
+
+    @staticmethod
+    def record_batch_dev(kind, fmt, d_items, n, sources=(), d_effect=None, d_perm=None, d_mask=None,
+                         n_inst=0, inst_base=0, d_n=None, general=False):
+        """the mpx_record_batch of a record_log_dev call; sources: a list of dicts of device
+        pointers (or devbuf.DevArrays) cmd_off / op / key / val with n_frames, n_cmds, n_recs. The
+        batch keeps its source array alive."""
+        def ptr_of(x, keep, t):
+            return getattr(x, "ptr", x)
+        src, _ = Engine._store_srcs(sources, ptr_of)
+        p = [getattr(x, "ptr", x) for x in (d_items, d_effect, d_mask, d_n, d_perm)]
+        b = _lib.MpxRecordBatch(kind, R.LR_GENERAL if general else 0, fmt, 0, p[0], p[1], p[2], n,
+                                p[3], p[4], src if len(sources) else None, len(sources), n_inst,
+                                inst_base, 0)
+        b._src_keep = src
+        return b
 
     # ---- instance-log encoding (SURVEY §8(f) ranks 3, 4) ------------------------------------
     def encode_log(self, fmt, recs, cmd_off, op, key, val):

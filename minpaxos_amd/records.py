@@ -189,6 +189,24 @@ STORE_SRC = np.dtype([("cmd_off", "<u8"), ("n_frames", "<u8"), ("op", "<u8"), ("
 assert STORE_RESULT.itemsize == 32 and STORE_SRC.itemsize == 56
 
 
+# record assembly (mpx_record_log): the kinds, the CLASSIC metadata format (beside LOG_DURABLE), the
+# call flag, the result flag, the one-launch bounds, the metadata bytes per format and
+# mpx_record_result
+LR_ACCEPTS, LR_COMMITS, LR_SENDS, LR_DECIDED = 0, 1, 2, 3
+LOG_DURABLE_CLASSIC = 2
+LR_GENERAL = 1
+LR_FULL = 1
+LR_ONE_LAUNCH_ITEMS, LR_ONE_LAUNCH_CMDS = 1024, 8192
+LR_HEADER_BYTES = {1: 12, LOG_DURABLE_CLASSIC: 5}
+RECORD_RESULT = np.dtype([("n_recs", "<u8"), ("n_cmds", "<u8"), ("n_bytes", "<u8"), ("flags", "<u8")])
+assert RECORD_RESULT.itemsize == 32
+
+
+def record_bound(n, m):
+    """mpx_record_bound: the most bytes n items carrying m commands can record, either format"""
+    return 12 * n + 17 * m
+
+
 def commit_frame_bytes(n_cmds):
     """one full Commit on a peer connection (code byte + Marshal)"""
     return 13 + varint_len(n_cmds) + 17 * n_cmds
