@@ -1,6 +1,8 @@
 // engine_host.hpp — the host side's private parts that more than one translation unit of the
 // C-ABI layer needs (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp, store.cpp, record.cpp): the handle,
 // error reporting, the families' scratch buffers and the staging arena of the host-pointer forms.
+// The command sources of store.cpp and record.cpp (their checks, the pre-check of an item's
+// commands, their staging) are cmd_src_host.hpp's, the host side of the kernels' assemble.hpp.
 // Internal: nothing here is ABI.
 #pragma once
 #include <hip/hip_runtime.h>

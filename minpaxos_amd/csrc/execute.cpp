@@ -1,7 +1,7 @@
 // execute.cpp — the C ABI of execute assembly (mpx_execute_gather[_reserve|_dev], include/mpx.h)
 // over the launcher of execute.hip: validation, then, for the host form, Stage staging around the
 // _dev form, like the other host-pointer entry points (engine.cpp, order.cpp, client.cpp,
-// replies.cpp).
+// replies.cpp). The kernels' pieces shared with the other assembly families are assemble.hpp's.
 #include <algorithm>
 #include <cstdint>
 #include <string>

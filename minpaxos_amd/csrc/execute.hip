@@ -18,8 +18,10 @@
 //   k_xg_finish  the result record
 // Launches: 8. A call of at most MPX_XG_ONE_LAUNCH_INST slots and MPX_XG_ONE_LAUNCH_CMDS commands
 // of capacity is one kernel in one workgroup: a slot per thread, stops and offsets in LDS.
+// The pieces shared with the other assembly families are assemble.hpp's.
 #include <algorithm>
 
+#include "assemble.hpp"
 #include "common.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // k_zero_u64: this unit launches no copy of it
@@ -102,11 +104,6 @@ __device__ __forceinline__ uint32_t xg_len(const XgArgs& a, const XgSlot& s, uin
     return s.n;
 }
 
-// (every lane of the wave calls)
-__device__ __forceinline__ void xg_raise(uint32_t* err, uint32_t bits) {
-    if (ballot(bits != 0) != 0 && lane_id() == 0) raise_err(err, kErrInval);
-}
-
 // executed_out of group g given its stop word, and what the result record counts
 __device__ __forceinline__ int64_t xg_cursor(const XgArgs& a, const XgGroup& G, uint32_t stop) {
     if (!G.ok || G.ex >= G.cu) return G.ex;
@@ -123,17 +120,6 @@ struct XgOff {
     const uint64_t* off;
     __device__ __forceinline__ uint64_t operator()(uint32_t i) const { return off[i]; }
 };
-// the instance of output position p, given off(l) <= p < off(h): the last one that starts at or
-// before p (the empty ones before it start there too and are passed over)
-__device__ __forceinline__ uint32_t xg_inst_of(const XgOff& off, uint64_t p, uint32_t l, uint32_t h) {
-    while (h - l > 1) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (off(mid) <= p) l = mid;
-        else h = mid;
-    }
-    return l;
-}
-
 // Positions p0 .. p0 + 3 (p0 a multiple of 4): the first n_real are gathered commands whose
 // instances lie in [i_lo, i_hi], the others up to n_out pad commands {NONE, key p, 0}.
 __device__ __forceinline__ void xg_emit4(const XgArgs& a, uint64_t p0, uint32_t n_real,
@@ -149,7 +135,7 @@ __device__ __forceinline__ void xg_emit4(const XgArgs& a, uint64_t p0, uint32_t 
         o[j] = 0, k[j] = p, v[j] = 0;
         if ((uint32_t)j < n_real) {
             if (j == 0 || p >= end) {
-                inst = xg_inst_of(off, p, j ? inst + 1 : i_lo, i_hi + 1);
+                inst = last_at_or_before(off, p, j ? inst + 1 : i_lo, i_hi + 1);
                 begin = off(inst), end = off(inst + 1);
                 first = a.inst[inst].first_cmd;
             }
@@ -159,6 +145,7 @@ __device__ __forceinline__ void xg_emit4(const XgArgs& a, uint64_t p0, uint32_t 
             v[j] = (uint64_t)a.src_val[src];
         }
     }
+    // (not assemble.hpp's store4_cmds: its test per array costs the gather 1-3 % on aligned arrays)
     uint8_t* const d_op = a.op + p0;
     int64_t *const d_key = a.key + p0, *const d_val = a.val + p0;
     if (n_out >= kXgPer) {
@@ -254,7 +241,7 @@ __global__ __launch_bounds__(kXgT) void k_xg_stop(XgArgs a, uint32_t* __restrict
             tail_bad[u] = tb;
         }
     }
-    xg_raise(a.err, ebits);
+    raise_bits(a.err, ebits, kErrInval);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < kXgPer; ++k) {
@@ -290,7 +277,7 @@ __global__ __launch_bounds__(kXgT) void k_xg_mark(XgArgs a, const uint32_t* __re
             len[idx] = run ? xg_len(a, s, ebits) : 0u;
         }
     }
-    xg_raise(a.err, ebits);
+    raise_bits(a.err, ebits, kErrInval);
 }
 
 // ---- pass 4: a tile of output positions per workgroup -------------------------------------------
@@ -327,14 +314,9 @@ __global__ __launch_bounds__(kXgT) void k_xg_groups(XgArgs a, uint32_t* __restri
     if (i < a.n_sends && a.ret_first) a.ret_first[i] = a.n_inst ? xg_ret_first(a, i, off) : 0;
     const uint32_t moved = (uint32_t)__syncthreads_count(ran != 0);
     if ((uint64_t)blockIdx.x * kXgT >= a.n_groups) return;  // a block of sends only
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) ran += shfl_any(ran, lane_id() ^ d);
-    if (lane_id() == 0) ws[threadIdx.x / kWave] = ran;
-    __syncthreads();
+    ran = block_sum<uint64_t, kXgT>(ran, ws);
     if (threadIdx.x == 0) {
-        uint64_t s = 0;
-        for (int x = 0; x < kXgT / kWave; ++x) s += ws[x];
-        part_inst[blockIdx.x] = s;
+        part_inst[blockIdx.x] = ran;
         part_moved[blockIdx.x] = moved;
     }
 }
@@ -348,6 +330,7 @@ __global__ __launch_bounds__(kXgFinT) void k_xg_finish(const uint64_t* __restric
     __shared__ uint64_t ws[2][kXgFinT / kWave];
     uint64_t ran = 0, moved = 0;
     for (uint32_t i = threadIdx.x; i < nb; i += kXgFinT) ran += part_inst[i], moved += part_moved[i];
+    // (not two of assemble.hpp's block_sum: the two values share the shuffles' rounds and one barrier)
 #pragma unroll
     for (int d = kWave / 2; d >= 1; d >>= 1) {
         ran += shfl_any(ran, lane_id() ^ d);
@@ -389,13 +372,9 @@ __global__ __launch_bounds__(kXgOneT) void k_xg_one(XgArgs a) {
         a.mask[t] = run ? 1 : 0;
         if (run) len = xg_len(a, s, ebits);
     }
-    xg_raise(a.err, ebits);
-    const uint64_t incl = wave_incl_scan((uint64_t)len, ScanSum64{});
-    if (lane_id() == kWave - 1) ws[t / kWave] = incl;
-    __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < t / kWave; ++w) before += ws[w];
-    s_off[t + 1] = before + incl;
+    // (not assemble.hpp's raise_bits: testing the one bit costs this kernel two scalar registers)
+    if (ballot(ebits != 0) != 0 && lane_id() == 0) raise_err(a.err, kErrInval);
+    s_off[t + 1] = block_excl_scan<uint64_t, kXgOneT>((uint64_t)len, ws) + len;
     if (t == 0) s_off[0] = 0;
     __syncthreads();
     const uint64_t total = s_off[a.n_inst];

@@ -1,11 +1,13 @@
 // record.cpp — the C ABI of record assembly (mpx_record_log[_reserve|_dev], mpx_record_bound,
 // include/mpx.h) over the launcher of record.hip: validation, then, for the host form, Stage staging
 // around the _dev form, like the other host-pointer entry points (engine.cpp, order.cpp, client.cpp,
-// replies.cpp, execute.cpp, store.cpp).
+// replies.cpp, execute.cpp, store.cpp). The command sources' checks, the pre-check of an item's
+// commands and their staging are cmd_src_host.hpp's, shared with store.cpp.
 #include <algorithm>
 #include <cstdint>
 #include <string>
 
+#include "cmd_src_host.hpp"
 #include "engine_host.hpp"
 #include "kernels.hpp"
 
@@ -43,13 +45,8 @@ int record_args(mpx_engine* e, const mpx_record_batch* b, const uint8_t* out, si
                  (b->kind == MPX_LR_DECIDED && b->n_inst && !b->mask)))
         return fail(e, MPX_E_INVAL, "null argument");
     if (msgs(b) && b->n_src > 1 && !b->perm) return fail(e, MPX_E_INVAL, "more than one source needs perm");
-    uint64_t recs = 0;
-    for (size_t s = 0; s < n_src(b); ++s) {
-        const mpx_store_src& x = b->src[s];
-        if ((x.n_cmds && (!x.op || !x.key || !x.val)) || (x.n_frames && !x.cmd_off))
-            return fail(e, MPX_E_INVAL, "null argument");
-        recs += x.n_recs;
-    }
+    uint64_t recs;
+    CK(src_args(e, b->src, n_src(b), &recs));
     if (b->kind != MPX_LR_DECIDED && recs < b->n)
         return fail(e, MPX_E_INVAL, "the sources hold fewer records than n");
     return MPX_OK;
@@ -92,11 +89,8 @@ int mpx_record_log(mpx_engine* e, const mpx_record_batch* b, uint8_t* out, size_
     // the device kernels report these through the error word; here they answer before any launch:
     // the recording items, judged in array order as the kernels judge each
     const size_t ns = n_src(b);
-    uint64_t rec_end[MPX_SC_MAX_SRC], recs = 0;
-    for (size_t s = 0; s < ns; ++s) rec_end[s] = recs += b->src[s].n_recs;
-    if (b->perm && msgs(b))
-        for (size_t i = 0; i < b->n; ++i)
-            if (b->perm[i] >= recs) return fail(e, MPX_E_INVAL, "a perm entry is out of range");
+    const SrcIndex idx(b->src, ns);
+    if (msgs(b)) CK(perm_args(e, idx, b->perm, b->n));
     const uint64_t hdr = b->format == MPX_LOG_DURABLE ? 12 : 5;
     bool any = false;
     uint64_t total = 0, rel_lo = 0, rel_hi = 0;
@@ -110,27 +104,12 @@ int mpx_record_log(mpx_engine* e, const mpx_record_batch* b, uint8_t* out, size_
             } else {
                 cmds = (b->effect[i] & MPX_CH_CMDS) && m.value_id != MPX_VALUE_KEEP;
             }
-            if (cmds) {
-                const uint64_t p = b->perm ? b->perm[i] : i;
-                size_t s = 0;
-                while (s + 1 < ns && p >= rec_end[s]) ++s;
-                const mpx_store_src& x = b->src[s];
-                if (m.value_id >= x.n_frames)
-                    return fail(e, MPX_E_INVAL, "a recording item's value_id is not a frame of its source");
-                const uint64_t lo = x.cmd_off[m.value_id], hi = x.cmd_off[m.value_id + 1];
-                if (hi < lo) return fail(e, MPX_E_INVAL, "cmd_off decreases");
-                if (hi > x.n_cmds || hi - lo >= 0xFFFFFFFFull)
-                    return fail(e, MPX_E_INVAL, "a recording item's command range leaves [0, n_cmds)");
-                len = hi - lo;
-            }
+            if (cmds) CK(resolve_msg(e, idx, b->perm ? b->perm[i] : i, m.value_id, "recording", &len));
         } else {
             const mpx_accept_send& x = ((const mpx_accept_send*)b->items)[i];
             if (!(x.flags & MPX_PH_ACCEPT)) continue;
             if (b->kind == MPX_LR_SENDS) {
-                const uint64_t lo = x.first_cmd;
-                len = x.n_cmds;
-                if (lo > b->src[0].n_cmds || len > b->src[0].n_cmds - lo || len == 0xFFFFFFFFull)
-                    return fail(e, MPX_E_INVAL, "a recording item's command range leaves [0, n_cmds)");
+                CK(resolve_send(e, b->src[0], x, "recording", &len));
             } else {
                 const int64_t rel = (int64_t)x.instance - b->inst_base;
                 if (rel < 0 || (uint64_t)rel >= b->n_inst)
@@ -155,38 +134,19 @@ int mpx_record_log(mpx_engine* e, const mpx_record_batch* b, uint8_t* out, size_
                s_perm = L.add(b->perm && msgs(b) ? b->n * sizeof(uint32_t) : 0), s_mask = L.add(n_span),
                s_out = L.add(n_out), s_ioff = L.add(item_off ? (b->n + 1) * sizeof(uint64_t) : 0),
                s_res = L.add(sizeof(mpx_record_result));
-    Slot s_src[MPX_SC_MAX_SRC][4];
-    for (size_t s = 0; s < ns; ++s) {
-        const mpx_store_src& x = b->src[s];
-        s_src[s][0] = L.add(x.n_frames ? (x.n_frames + 1) * sizeof(uint64_t) : 0);
-        s_src[s][1] = L.add(x.n_cmds);
-        s_src[s][2] = L.add(x.n_cmds * sizeof(int64_t));
-        s_src[s][3] = L.add(x.n_cmds * sizeof(int64_t));
-    }
+    StagedSrcs srcs(L, b->src, ns);
     CK(L.commit());
     CK(L.in(s_items, b->items));
     if (msgs(b)) CK(L.in(s_eff, b->effect));
     if (b->perm && msgs(b)) CK(L.in(s_perm, b->perm));
     if (n_span) CK(L.in(s_mask, b->mask + rel_lo));
-    mpx_store_src d_src[MPX_SC_MAX_SRC];
-    for (size_t s = 0; s < ns; ++s) {
-        const mpx_store_src& x = b->src[s];
-        CK(L.in(s_src[s][0], x.cmd_off));
-        CK(L.in(s_src[s][1], x.op));
-        CK(L.in(s_src[s][2], x.key));
-        CK(L.in(s_src[s][3], x.val));
-        d_src[s] = x;
-        d_src[s].cmd_off = L.at<uint64_t>(s_src[s][0], x.n_frames ? x.cmd_off : nullptr);
-        d_src[s].op = L.at<uint8_t>(s_src[s][1], x.n_cmds ? x.op : nullptr);
-        d_src[s].key = L.at<int64_t>(s_src[s][2], x.n_cmds ? x.key : nullptr);
-        d_src[s].val = L.at<int64_t>(s_src[s][3], x.n_cmds ? x.val : nullptr);
-    }
+    CK(srcs.in());
     mpx_record_batch d = *b;
     d.items = L.at<char>(s_items, b->n ? b->items : nullptr);
     d.effect = msgs(b) ? L.at<uint8_t>(s_eff, b->effect) : nullptr;
     d.perm = msgs(b) ? L.at<uint32_t>(s_perm, b->perm) : nullptr;
     d.mask = n_span ? L.at<uint8_t>(s_mask) - rel_lo : b->mask;  // (no accepted slot: not read)
-    d.src = d_src, d.n_src = ns;
+    d.src = srcs.dev(), d.n_src = ns;
     // (a run that does not fit writes nothing: the device form gets the caller's capacity and an
     // empty slot)
     CK(mpx_record_log_dev(e, &d, L.at<uint8_t>(s_out), out_cap, L.at<uint64_t>(s_ioff, item_off),

@@ -10,8 +10,8 @@
 // items' records back to back in array order. Nothing here is per window slot: the passes run over
 // the n items and the bytes written.
 //   k_lr_mark   an item per thread: whether it records, its record's bytes (0: it does not), and
-//               where its commands start in its source (store.hip's resolution: the source of
-//               record p = perm[i] by the prefix sums of n_recs)
+//               where its commands start in its source (assemble.hpp's msg_cmds / send_cmds, as
+//               store.hip resolves them)
 //   scan.hpp    the sizes' exclusive scan, in place: where every item's record starts (item_off
 //               beside it when the caller asked)
 //   k_lr_emit   balanced over OUTPUT bytes: an 8 KB window of the run per workgroup (a grid of at
@@ -27,6 +27,7 @@
 // and positions in LDS, the same window loop.
 #include <algorithm>
 
+#include "assemble.hpp"
 #include "common.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // k_zero_u64: this unit launches no copy of it
@@ -45,17 +46,9 @@ constexpr int kLrWinBytes = kLrT * 16 * 2;   // 8 KB of output per window (logen
 constexpr int kLrWinWords = kLrWinBytes / 4;
 constexpr int kLrGrid = 2048;                // workgroups of k_lr_emit at most (six resident per CU)
 constexpr int kLrOnePer = MPX_LR_ONE_LAUNCH_ITEMS / kLrT;  // items per thread of the one-launch kernel
-constexpr uint64_t kLrPosMask = (1ull << 56) - 1;
 static_assert(MPX_LR_ONE_LAUNCH_ITEMS % kLrT == 0, "the one-launch kernel takes whole items per thread");
 static_assert(sizeof(mpx_accept_msg) == 16 && sizeof(mpx_accept_send) == 32, "vector loads per record");
 static_assert(sizeof(mpx_record_result) == 32, "the result record");
-
-struct LrSrc {
-    const uint64_t* cmd_off;
-    const uint8_t* op;
-    const int64_t *key, *val;
-    uint64_t n_frames, n_cmds, rec_end;  // rec_end: the records of sources 0 .. s
-};
 
 // the call, by value to every kernel
 struct LrArgs {
@@ -70,29 +63,8 @@ struct LrArgs {
     uint32_t* err;
     int32_t inst_base;
     uint32_t kind, format, n_src;
-    LrSrc src[MPX_SC_MAX_SRC];
+    CmdSrc src[MPX_SC_MAX_SRC];
 };
-
-// the sources into LDS (constant indices into the kernel arguments; the kernels index the table
-// by a lane's own source). Every thread calls.
-__device__ __forceinline__ void lr_sources(const LrArgs& a, LrSrc* S) {
-#pragma unroll
-    for (int s = 0; s < MPX_SC_MAX_SRC; ++s)
-        if ((int)threadIdx.x == s && (uint32_t)s < a.n_src) S[s] = a.src[s];
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint64_t lr_n_eff(const LrArgs& a) {
-    if (!a.d_n) return a.n;
-    const uint64_t d = *a.d_n;
-    return d < a.n ? d : a.n;
-}
-
-// (every lane of the wave calls)
-__device__ __forceinline__ void lr_raise(uint32_t* err, uint32_t bits) {
-    if (ballot((bits & kErrInval) != 0) != 0 && lane_id() == 0) raise_err(err, kErrInval);
-    if (ballot((bits & kErrNil) != 0) != 0 && lane_id() == 0) raise_err(err, kErrNil);
-}
 
 __device__ __forceinline__ uint32_t lr_hdr(const LrArgs& a) { return a.format == MPX_LOG_DURABLE ? 12u : 5u; }
 __device__ __forceinline__ uint32_t lr_status(const LrArgs& a) {
@@ -101,15 +73,15 @@ __device__ __forceinline__ uint32_t lr_status(const LrArgs& a) {
 }
 
 // What item i records: bytes == 0 when it does not (also a faulty one: its bit is raised).
-// pos = the source in the top byte, the first command's index in it below.
+// pos: assemble.hpp's cmd_pos of its first command.
 struct LrItem {
     uint64_t bytes, pos;
 };
-__device__ __forceinline__ LrItem lr_item(const LrArgs& a, const LrSrc* S, uint64_t i, uint64_t n_eff,
+__device__ __forceinline__ LrItem lr_item(const LrArgs& a, const CmdSrc* S, uint64_t i, uint64_t n_eff,
                                           uint32_t& ebits) {
     LrItem r{0, 0};
     if (i >= n_eff) return r;
-    uint64_t lo = 0, len = 0, sid = 0;
+    CmdRange c{0, 0, 0, true};  // (metadata only: no commands)
     if (a.kind <= MPX_LR_COMMITS) {
         const uint4 m = *(reinterpret_cast<const uint4*>(a.items) + i);  // {instance, ballot, leader, value}
         const uint32_t eff = a.effect[i];
@@ -120,35 +92,17 @@ __device__ __forceinline__ LrItem lr_item(const LrArgs& a, const LrSrc* S, uint6
             cmds = (eff & MPX_CH_CMDS) && m.w != MPX_VALUE_KEEP;  // a CommitShort: metadata only
         }
         if (cmds) {
-            const uint64_t p = a.perm ? a.perm[i] : i;
-            if (p >= a.n_recs) {
-                ebits |= kErrInval;
-                return r;
-            }
-            while (sid + 1 < a.n_src && p >= S[sid].rec_end) ++sid;
-            if (m.w >= S[sid].n_frames) {
-                ebits |= kErrInval;
-                return r;
-            }
-            lo = S[sid].cmd_off[m.w];
-            const uint64_t hi = S[sid].cmd_off[m.w + 1];
-            if (hi < lo || hi > S[sid].n_cmds || hi - lo >= 0xFFFFFFFFull) {
-                ebits |= kErrInval;
-                return r;
-            }
-            len = hi - lo;
+            c = msg_cmds(S, a.n_src, a.n_recs, a.perm, i, m.w, ebits);
+            if (!c.ok) return r;
         }
     } else {
         const uint4* x = reinterpret_cast<const uint4*>(a.items) + 2 * i;
         const uint4 h = x[0];  // {instance, ballot, last_committed, flags}
         if (!(h.w & MPX_PH_ACCEPT)) return r;
         if (a.kind == MPX_LR_SENDS) {
-            const uint4 c = x[1];  // {first_cmd, n_cmds, pad}
-            lo = (uint64_t)c.x | ((uint64_t)c.y << 32), len = c.z;
-            if (lo > S[0].n_cmds || len > S[0].n_cmds - lo || len == 0xFFFFFFFFull) {
-                ebits |= kErrInval;
-                return r;
-            }
+            const uint4 f = x[1];  // {first_cmd, n_cmds, pad}
+            c = send_cmds(S[0], (uint64_t)f.x | ((uint64_t)f.y << 32), f.z, ebits);
+            if (!c.ok) return r;
         } else {
             const int64_t rel = (int64_t)(int32_t)h.x - a.inst_base;
             if (rel < 0 || (uint64_t)rel >= a.n_inst) {
@@ -158,7 +112,7 @@ __device__ __forceinline__ LrItem lr_item(const LrArgs& a, const LrSrc* S, uint6
             if (!a.mask[rel]) return r;
         }
     }
-    r.bytes = lr_hdr(a) + 17 * len, r.pos = (sid << 56) | lo;
+    r.bytes = lr_hdr(a) + 17 * c.len, r.pos = cmd_pos(c.src, c.lo);
     return r;
 }
 
@@ -178,13 +132,7 @@ struct LrAccLds {
     __device__ __forceinline__ uint64_t off(uint64_t i) const { return o[i]; }
     __device__ __forceinline__ uint64_t pos(uint64_t i) const { return p[i]; }
     __device__ __forceinline__ uint64_t find(uint64_t q, int) const {
-        uint64_t lo = 0, hi = n;
-        while (hi - lo > 1) {
-            const uint64_t mid = lo + ((hi - lo) >> 1);
-            if (o[mid] <= q) lo = mid;
-            else hi = mid;
-        }
-        return lo;
+        return last_at_or_before([this](uint64_t i) { return o[i]; }, q, (uint64_t)0, n);
     }
 };
 
@@ -201,7 +149,7 @@ struct LrLds {
 // base + w * 8 KB (base = out rounded down to 16 bytes, `head` bytes before out), and image byte x
 // of it is output byte w * 8 KB + x - head. Every thread calls.
 template <typename Acc>
-__device__ __forceinline__ void lr_windows(const LrArgs& a, const LrSrc* S, const Acc& acc, uint64_t total,
+__device__ __forceinline__ void lr_windows(const LrArgs& a, const CmdSrc* S, const Acc& acc, uint64_t total,
                                            uint64_t w0, uint64_t w_step, LrLds& L) {
     const int t = (int)threadIdx.x;
     const uint32_t hdr = lr_hdr(a), status = lr_status(a);
@@ -252,8 +200,8 @@ __device__ __forceinline__ void lr_windows(const LrArgs& a, const LrSrc* S, cons
                     if (p >= pieces) continue;
                     const uint32_t x = piece_item(L.poff, p);
                     const uint64_t j = (uint64_t)L.i_lo[x] + (p - L.poff[x]), pos = L.i_pos[x];
-                    const LrSrc& s = S[pos >> 56];
-                    const uint64_t c = (pos & kLrPosMask) + j;
+                    const CmdSrc& s = S[cmd_pos_src(pos)];
+                    const uint64_t c = cmd_pos_lo(pos) + j;
                     o[u] = s.op[c], k[u] = (uint64_t)s.key[c], v[u] = (uint64_t)s.val[c];
                     at[u] = L.i_cs[x] + 17 * (int64_t)j;
                 }
@@ -303,13 +251,13 @@ struct LrOffOut {
 // (n + 1 entries: the last, of size 0, becomes the total)
 __global__ __launch_bounds__(kLrT) void k_lr_mark(LrArgs a, uint64_t* __restrict__ size,
                                                   uint64_t* __restrict__ pos, uint32_t* __restrict__ part) {
-    __shared__ LrSrc S[MPX_SC_MAX_SRC];
-    lr_sources(a, S);
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
+    cmd_sources(a.src, a.n_src, S);
     const uint64_t i = (uint64_t)blockIdx.x * kLrT + threadIdx.x;
     uint32_t ebits = 0;
-    const LrItem x = lr_item(a, S, i, lr_n_eff(a), ebits);
+    const LrItem x = lr_item(a, S, i, n_eff(a.d_n, a.n), ebits);
     if (i <= a.n) size[i] = x.bytes, pos[i] = x.pos;
-    lr_raise(a.err, ebits);
+    raise_bits(a.err, ebits, kErrInval | kErrNil);
     const uint32_t c = (uint32_t)__syncthreads_count(x.bytes != 0);
     if (threadIdx.x == 0) part[blockIdx.x] = c;
 }
@@ -318,10 +266,10 @@ __global__ __launch_bounds__(kLrT) void k_lr_mark(LrArgs a, uint64_t* __restrict
 __global__ __launch_bounds__(kLrT) void k_lr_emit(LrArgs a, const uint64_t* __restrict__ off,
                                                   const uint64_t* __restrict__ pos,
                                                   const uint32_t* __restrict__ part, uint32_t n_part) {
-    __shared__ LrSrc S[MPX_SC_MAX_SRC];
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
     __shared__ LrLds L;
     __shared__ uint64_t ws[kLrT / kWave];
-    lr_sources(a, S);
+    cmd_sources(a.src, a.n_src, S);
     const uint32_t t = threadIdx.x;
     const uint64_t total = off[a.n];
     const bool full = total > a.out_cap;
@@ -329,44 +277,33 @@ __global__ __launch_bounds__(kLrT) void k_lr_emit(LrArgs a, const uint64_t* __re
     if (blockIdx.x) return;
     uint64_t recs = 0;
     for (uint32_t x = t; x < n_part; x += kLrT) recs += part[x];
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) recs += shfl_any(recs, lane_id() ^ d);
-    if (lane_id() == 0) ws[t / kWave] = recs;
-    __syncthreads();
-    if (t == 0) {
-        recs = 0;
-        for (int w = 0; w < kLrT / kWave; ++w) recs += ws[w];
-        lr_result(a, recs, total, full);
-    }
+    recs = block_sum<uint64_t, kLrT>(recs, ws);
+    if (t == 0) lr_result(a, recs, total, full);
 }
 
 // ---- one launch: a replica-sized batch in one workgroup, no scratch ------------------------------
 __global__ __launch_bounds__(kLrT) void k_lr_one(LrArgs a) {
-    __shared__ LrSrc S[MPX_SC_MAX_SRC];
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
     __shared__ LrLds L;
     __shared__ uint64_t s_off[MPX_LR_ONE_LAUNCH_ITEMS + 1], s_pos[MPX_LR_ONE_LAUNCH_ITEMS];
     __shared__ uint64_t ws[kLrT / kWave];
     __shared__ uint32_t s_recs;
-    lr_sources(a, S);
+    cmd_sources(a.src, a.n_src, S);
     const uint32_t t = threadIdx.x;
     if (t == 0) s_recs = 0;
-    const uint64_t n_eff = lr_n_eff(a);
+    const uint64_t n_items = n_eff(a.d_n, a.n);
     // items kLrOnePer * t ..: their sizes, scanned
     uint32_t ebits = 0, recs = 0;
     uint64_t bytes[kLrOnePer], sum = 0;
 #pragma unroll
     for (int k = 0; k < kLrOnePer; ++k) {
-        const LrItem x = lr_item(a, S, (uint64_t)t * kLrOnePer + k, n_eff, ebits);
+        const LrItem x = lr_item(a, S, (uint64_t)t * kLrOnePer + k, n_items, ebits);
         bytes[k] = x.bytes, s_pos[t * kLrOnePer + k] = x.pos;
         sum += x.bytes, recs += x.bytes != 0;
     }
-    lr_raise(a.err, ebits);
-    const uint64_t incl = wave_incl_scan(sum, ScanSum64{});
-    if (lane_id() == kWave - 1) ws[t / kWave] = incl;
-    __syncthreads();
+    raise_bits(a.err, ebits, kErrInval | kErrNil);
+    uint64_t run = block_excl_scan<uint64_t, kLrT>(sum, ws);
     if (recs) atomicAdd(&s_recs, recs);
-    uint64_t run = incl - sum;
-    for (uint32_t w = 0; w < t / kWave; ++w) run += ws[w];
 #pragma unroll
     for (int k = 0; k < kLrOnePer; ++k) {
         s_off[t * kLrOnePer + k] = run;
@@ -411,13 +348,8 @@ hipError_t launch_record_log(const mpx_record_batch* b, uint8_t* out, uint64_t o
     a.out = out, a.item_off = item_off, a.res = res, a.err = err;
     a.inst_base = b->inst_base, a.kind = b->kind, a.format = b->format;
     a.n_src = b->kind == MPX_LR_DECIDED ? 0u : (uint32_t)b->n_src;
-    uint64_t recs = 0, cmds = 0;
-    for (uint32_t s = 0; s < a.n_src; ++s) {
-        const mpx_store_src& x = b->src[s];
-        recs += x.n_recs, cmds += x.n_cmds;
-        a.src[s] = LrSrc{x.cmd_off, x.op, x.key, x.val, x.n_frames, x.n_cmds, recs};
-    }
-    a.n_recs = recs;
+    uint64_t cmds;
+    fill_cmd_sources(b->src, a.n_src, a.src, a.n_recs, cmds);
     if (!n || (!(b->flags & MPX_LR_GENERAL) && n <= MPX_LR_ONE_LAUNCH_ITEMS && cmds <= MPX_LR_ONE_LAUNCH_CMDS)) {
         k_lr_one<<<1, kLrT, 0, stream>>>(a);  // (also a call of no item: the kernel writes the result)
         return hipGetLastError();

@@ -1,6 +1,7 @@
 // replies.cpp — the C ABI of reply assembly (mpx_build_replies[_reserve|_dev], include/mpx.h)
 // over the launcher of replies.hip: validation, then, for the host form, Stage staging around the
-// _dev form, like the other host-pointer entry points (engine.cpp, order.cpp, client.cpp).
+// _dev form, like the other host-pointer entry points (engine.cpp, order.cpp, client.cpp). The
+// kernels' pieces shared with the other assembly families are assemble.hpp's.
 #include <algorithm>
 #include <cstdint>
 #include <string>

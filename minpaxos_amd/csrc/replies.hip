@@ -14,6 +14,8 @@
 // result record (no ticket, no atomics: the family keeps no control words). Launches: 6.
 // A call of at most MPX_RB_ONE_LAUNCH_SLOTS slots and MPX_RB_ONE_LAUNCH_REPLIES records of
 // capacity is one kernel in one workgroup: a slot per thread, the scan in LDS, the same tiles.
+// The pieces shared with the other assembly families are assemble.hpp's.
+#include "assemble.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
@@ -91,29 +93,11 @@ __device__ __forceinline__ RbSlot rb_slot(const RbArgs& a, uint64_t s) {
     return r;
 }
 
-// (every lane of the wave calls)
-__device__ __forceinline__ void rb_raise(uint32_t* err, uint32_t bits) {
-    const bool nil = ballot((bits & kErrNil) != 0) != 0, inval = ballot((bits & kErrInval) != 0) != 0;
-    if (lane_id() == 0 && (nil || inval))
-        raise_err(err, (nil ? kErrNil : 0u) | (inval ? kErrInval : 0u));
-}
-
 // the scanned offsets, in global memory (general path) or in LDS (one launch)
 struct RbOff {
     const uint64_t* off;
     __device__ __forceinline__ uint64_t operator()(uint32_t s) const { return off[s]; }
 };
-
-// the slot of output index i, given off(l) <= i < off(h): the last slot that starts at or before
-// i (the empty slots before it start there too and are passed over)
-__device__ __forceinline__ uint32_t rb_slot_of(const RbOff& off, uint64_t i, uint32_t l, uint32_t h) {
-    while (h - l > 1) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (off(mid) <= i) l = mid;
-        else h = mid;
-    }
-    return l;
-}
 
 // One tile: output indices [lo, min(lo + kRbTile, cap)), of which those below `total` are replies
 // and, with padding, the others pad records. All threads of the workgroup call (T of them); img
@@ -128,8 +112,8 @@ __device__ __forceinline__ void rb_emit_tile(const RbArgs& a, uint64_t lo, uint6
     if (!n_out) return;  // (the same in every thread)
     // the first and the last slot under the tile's replies
     if (n_real) {
-        if (t == 0) rng[0] = rb_slot_of(off, lo, 0u, (uint32_t)a.n_sends);
-        if (t == kWave) rng[1] = rb_slot_of(off, lo + n_real - 1, 0u, (uint32_t)a.n_sends);
+        if (t == 0) rng[0] = last_at_or_before(off, lo, 0u, (uint32_t)a.n_sends);
+        if (t == kWave) rng[1] = last_at_or_before(off, lo + n_real - 1, 0u, (uint32_t)a.n_sends);
     }
     __syncthreads();
     const uintptr_t dst = (uintptr_t)a.recs + lo * sizeof(mpx_reply_rec);
@@ -143,7 +127,7 @@ __device__ __forceinline__ void rb_emit_tile(const RbArgs& a, uint64_t lo, uint6
         uint2 value = make_uint2(0u, 0u), ts = make_uint2(0u, 0u), tail = make_uint2(0u, a.pad_client);
         if (r < n_real) {
             const uint64_t i = lo + r;
-            const uint32_t s = rb_slot_of(off, i, s_lo, s_hi + 1);
+            const uint32_t s = last_at_or_before(off, i, s_lo, s_hi + 1);
             const uint64_t k_in = i - off(s);
             const uint4 h1 = reinterpret_cast<const uint4*>(a.sends + s)[1];
             const uint64_t first = (uint64_t)h1.x | ((uint64_t)h1.y << 32);
@@ -202,7 +186,7 @@ __global__ __launch_bounds__(kRbT) void k_rb_count(RbArgs a, uint32_t* __restric
         r = rb_slot(a, s);
         cnt[s] = r.cnt;
     }
-    rb_raise(a.err, r.err);
+    raise_bits(a.err, r.err, kErrInval | kErrNil);
     const uint32_t n_sel = (uint32_t)__syncthreads_count(r.sel);
     if (threadIdx.x == 0) bsel[blockIdx.x] = n_sel;
 }
@@ -223,13 +207,8 @@ __global__ __launch_bounds__(kRbFinT) void k_rb_finish(const uint64_t* __restric
     __shared__ uint64_t ws[kRbFinT / kWave];
     uint64_t mine = 0;
     for (uint32_t i = threadIdx.x; i < nb; i += kRbFinT) mine += bsel[i];
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) mine += shfl_any(mine, lane_id() ^ d);
-    if (lane_id() == 0) ws[threadIdx.x / kWave] = mine;
-    __syncthreads();
+    const uint64_t n_slots = block_sum<uint64_t, kRbFinT>(mine, ws);
     if (threadIdx.x == 0) {
-        uint64_t n_slots = 0;
-        for (int w = 0; w < kRbFinT / kWave; ++w) n_slots += ws[w];
         res->n_replies = n_sends ? off[n_sends] : 0;
         res->n_slots = n_slots;
     }
@@ -244,14 +223,9 @@ __global__ __launch_bounds__(kRbOneT) void k_rb_one(RbArgs a) {
     const uint32_t t = threadIdx.x;
     RbSlot r{0, false, 0};
     if (t < a.n_sends) r = rb_slot(a, t);
-    rb_raise(a.err, r.err);
+    raise_bits(a.err, r.err, kErrInval | kErrNil);
     const uint32_t n_sel = (uint32_t)__syncthreads_count(r.sel);
-    const uint64_t incl = wave_incl_scan((uint64_t)r.cnt, ScanSum64{});
-    if (lane_id() == kWave - 1) ws[t / kWave] = incl;
-    __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < t / kWave; ++w) before += ws[w];
-    s_off[t + 1] = before + incl;
+    s_off[t + 1] = block_excl_scan<uint64_t, kRbOneT>((uint64_t)r.cnt, ws) + r.cnt;
     if (t == 0) s_off[0] = 0;
     __syncthreads();
     const uint64_t total = s_off[a.n_sends];

@@ -1,12 +1,14 @@
 // store.cpp — the C ABI of store assembly (mpx_store_commands[_reserve|_dev],
 // mpx_store_compact[_reserve|_dev], include/mpx.h) over the launchers of store.hip: validation,
 // then, for the host forms, Stage staging around the _dev forms, like the other host-pointer entry
-// points (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp).
+// points (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp). The command sources' checks,
+// the pre-check of an item's commands and their staging are cmd_src_host.hpp's, shared with record.cpp.
 #include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "cmd_src_host.hpp"
 #include "engine_host.hpp"
 #include "kernels.hpp"
 
@@ -39,13 +41,8 @@ int store_args(mpx_engine* e, const mpx_store_batch* b, const mpx_store_arena* a
         return fail(e, MPX_E_INVAL, "null argument");
     if (b->kind == MPX_SC_MSGS && b->n_src > 1 && !b->perm)
         return fail(e, MPX_E_INVAL, "more than one source needs perm");
-    uint64_t recs = 0;
-    for (size_t s = 0; s < b->n_src; ++s) {
-        const mpx_store_src& x = b->src[s];
-        if ((x.n_cmds && (!x.op || !x.key || !x.val)) || (x.n_frames && !x.cmd_off))
-            return fail(e, MPX_E_INVAL, "null argument");
-        recs += x.n_recs;
-    }
+    uint64_t recs;
+    CK(src_args(e, b->src, b->n_src, &recs));
     if (recs < b->n) return fail(e, MPX_E_INVAL, "the sources hold fewer records than n");
     return MPX_OK;
 }
@@ -125,41 +122,25 @@ int mpx_store_commands(mpx_engine* e, const mpx_store_batch* b, const mpx_store_
     if (used > arena->cap) return fail(e, MPX_E_INVAL, "*used is past cap");
     // the device kernels report these through the error word; here they answer before any launch:
     // the storing items, judged in array order as the kernels judge each
-    uint64_t rec_end[MPX_SC_MAX_SRC], recs = 0;
-    for (size_t s = 0; s < b->n_src; ++s) rec_end[s] = recs += b->src[s].n_recs;
-    if (b->perm)
-        for (size_t i = 0; i < b->n; ++i)
-            if (b->perm[i] >= recs) return fail(e, MPX_E_INVAL, "a perm entry is out of range");
+    const SrcIndex idx(b->src, b->n_src);
+    CK(perm_args(e, idx, b->perm, b->n));
     bool any = false;
     int32_t prev = 0;
     uint32_t prev_len = 0;
     uint64_t total = 0, rel_lo = 0, rel_hi = 0;
     for (size_t i = 0; i < b->n; ++i) {
         int32_t instance;
-        uint64_t lo, len;
+        uint64_t len;
         if (b->kind == MPX_SC_MSGS) {
             const mpx_accept_msg& m = ((const mpx_accept_msg*)b->items)[i];
             if (!(b->effect[i] & b->store_mask) || m.value_id == MPX_VALUE_KEEP) continue;
             instance = m.instance;
-            const uint64_t p = b->perm ? b->perm[i] : i;
-            size_t s = 0;
-            while (s + 1 < b->n_src && p >= rec_end[s]) ++s;
-            const mpx_store_src& x = b->src[s];
-            if (m.value_id >= x.n_frames)
-                return fail(e, MPX_E_INVAL, "a storing item's value_id is not a frame of its source");
-            lo = x.cmd_off[m.value_id];
-            const uint64_t hi = x.cmd_off[m.value_id + 1];
-            if (hi < lo) return fail(e, MPX_E_INVAL, "cmd_off decreases");
-            if (hi > x.n_cmds || hi - lo >= 0xFFFFFFFFull)
-                return fail(e, MPX_E_INVAL, "a storing item's command range leaves [0, n_cmds)");
-            len = hi - lo;
+            CK(resolve_msg(e, idx, b->perm ? b->perm[i] : i, m.value_id, "storing", &len));
         } else {
             const mpx_accept_send& x = ((const mpx_accept_send*)b->items)[i];
             if (!(x.flags & (MPX_PH_ACCEPT | MPX_PH_PREPARE))) continue;
             instance = x.instance;
-            lo = x.first_cmd, len = x.n_cmds;
-            if (lo > b->src[0].n_cmds || len > b->src[0].n_cmds - lo || len == 0xFFFFFFFFull)
-                return fail(e, MPX_E_INVAL, "a storing item's command range leaves [0, n_cmds)");
+            CK(resolve_send(e, b->src[0], x, "storing", &len));
         }
         const int64_t rel = (int64_t)instance - b->inst_base;
         if (rel < 0 || (uint64_t)rel >= b->n_inst)
@@ -181,38 +162,19 @@ int mpx_store_commands(mpx_engine* e, const mpx_store_batch* b, const mpx_store_
                s_op = L.add(n_out), s_key = L.add(n_out * sizeof(int64_t)),
                s_val = L.add(n_out * sizeof(int64_t)), s_inst = L.add(n_span * sizeof(mpx_inst_cmds)),
                s_used = L.add(sizeof(uint64_t)), s_res = L.add(sizeof(mpx_store_result));
-    Slot s_src[MPX_SC_MAX_SRC][4];
-    for (size_t s = 0; s < b->n_src; ++s) {
-        const mpx_store_src& x = b->src[s];
-        s_src[s][0] = L.add(x.n_frames ? (x.n_frames + 1) * sizeof(uint64_t) : 0);
-        s_src[s][1] = L.add(x.n_cmds);
-        s_src[s][2] = L.add(x.n_cmds * sizeof(int64_t));
-        s_src[s][3] = L.add(x.n_cmds * sizeof(int64_t));
-    }
+    StagedSrcs srcs(L, b->src, b->n_src);
     CK(L.commit());
     CK(L.in(s_items, b->items));
     if (b->effect) CK(L.in(s_eff, b->effect));
     if (b->perm) CK(L.in(s_perm, b->perm));
     if (n_span) CK(L.in(s_inst, inst + rel_lo));
     CK(L.in(s_used, arena->used));
-    mpx_store_src d_src[MPX_SC_MAX_SRC];
-    for (size_t s = 0; s < b->n_src; ++s) {
-        const mpx_store_src& x = b->src[s];
-        CK(L.in(s_src[s][0], x.cmd_off));
-        CK(L.in(s_src[s][1], x.op));
-        CK(L.in(s_src[s][2], x.key));
-        CK(L.in(s_src[s][3], x.val));
-        d_src[s] = x;
-        d_src[s].cmd_off = L.at<uint64_t>(s_src[s][0], x.n_frames ? x.cmd_off : nullptr);
-        d_src[s].op = L.at<uint8_t>(s_src[s][1], x.n_cmds ? x.op : nullptr);
-        d_src[s].key = L.at<int64_t>(s_src[s][2], x.n_cmds ? x.key : nullptr);
-        d_src[s].val = L.at<int64_t>(s_src[s][3], x.n_cmds ? x.val : nullptr);
-    }
+    CK(srcs.in());
     mpx_store_batch d = *b;
     d.items = L.at<char>(s_items, b->n ? b->items : nullptr);
     d.effect = L.at<uint8_t>(s_eff, b->effect);
     d.perm = L.at<uint32_t>(s_perm, b->perm);
-    d.src = d_src;
+    d.src = srcs.dev();
     // the arena's appended range and the window's written span alone are staged: the kernels index
     // them from the arena's and the window's starts
     mpx_store_arena da{};

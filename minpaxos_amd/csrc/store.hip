@@ -9,8 +9,9 @@
 // the batch is grouped by instance, so of one instance's storing items the last wins: a storing
 // item loses exactly when the NEXT STORING item of the array names its instance. Nothing here is
 // per window slot: the passes run over the n items and the commands copied.
+// The pieces shared with the other assembly families are assemble.hpp's.
 //   k_st_mark   an item per thread: whether it stores, how many commands, and where they start in
-//               its source (the source of record p = perm[i] by the prefix sums of n_recs)
+//               its source (assemble.hpp's msg_cmds / send_cmds)
 //   scan.hpp    the storing items compacted into a list (their count beside it)
 //   k_st_win    a list entry per thread: it wins unless the next entry names its instance; the
 //               winners' lengths, the workgroups' winner counts, the cursor as the call found it
@@ -28,6 +29,7 @@
 // flagged slot a winner (5 launches).
 #include <algorithm>
 
+#include "assemble.hpp"
 #include "common.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // k_zero_u64: this unit launches no copy of it
@@ -55,13 +57,6 @@ static_assert(MPX_SC_MAX_SRC == MPX_ORDER_MAX_SRC, "a source per ordered connect
 static_assert(sizeof(mpx_accept_msg) == 16 && sizeof(mpx_accept_send) == 32 && sizeof(mpx_inst_cmds) == 16,
               "vector loads and stores per record");
 
-struct StSrc {
-    const uint64_t* cmd_off;
-    const uint8_t* op;
-    const int64_t *key, *val;
-    uint64_t n_frames, n_cmds, rec_end;  // rec_end: the records of sources 0 .. s
-};
-
 // the call, by value to every kernel
 struct StArgs {
     const void* items;
@@ -78,29 +73,8 @@ struct StArgs {
     uint32_t* err;
     int32_t inst_base;
     uint32_t kind, n_src, store_mask;
-    StSrc src[MPX_SC_MAX_SRC];
+    CmdSrc src[MPX_SC_MAX_SRC];
 };
-
-// the sources into LDS (constant indices into the kernel arguments; the kernels index the table
-// by a lane's own source). Every thread calls.
-__device__ __forceinline__ void st_sources(const StArgs& a, StSrc* S) {
-#pragma unroll
-    for (int s = 0; s < MPX_SC_MAX_SRC; ++s)
-        if ((int)threadIdx.x == s && (uint32_t)s < a.n_src) S[s] = a.src[s];
-    __syncthreads();
-}
-
-__device__ __forceinline__ uint64_t st_n_eff(const StArgs& a) {
-    if (!a.d_n) return a.n;
-    const uint64_t d = *a.d_n;
-    return d < a.n ? d : a.n;
-}
-
-// (every lane of the wave calls)
-__device__ __forceinline__ void st_raise(uint32_t* err, uint32_t bits) {
-    if (ballot((bits & kErrInval) != 0) != 0 && lane_id() == 0) raise_err(err, kErrInval);
-    if (ballot((bits & kErrNil) != 0) != 0 && lane_id() == 0) raise_err(err, kErrNil);
-}
 
 __device__ __forceinline__ int32_t st_instance(const StArgs& a, uint64_t i) {
     const char* p = (const char*)a.items + i * (a.kind == MPX_SC_SENDS ? sizeof(mpx_accept_send)
@@ -109,21 +83,21 @@ __device__ __forceinline__ int32_t st_instance(const StArgs& a, uint64_t i) {
 }
 
 // What item i stores: len == kStNone when it does not (also a faulty one: its bit is raised).
-// pos = the source in the top byte, the first command's index in it below.
+// pos: assemble.hpp's cmd_pos of its first command.
 struct StItem {
     uint32_t len;
     int32_t instance;
     uint64_t pos;
 };
-__device__ __forceinline__ StItem st_item(const StArgs& a, const StSrc* S, uint64_t i, uint64_t n_eff,
+__device__ __forceinline__ StItem st_item(const StArgs& a, const CmdSrc* S, uint64_t i, uint64_t n_eff,
                                           uint32_t& ebits) {
     StItem r{kStNone, 0, 0};
     if (i >= n_eff) return r;
-    uint64_t lo, len, sid = 0;
+    CmdRange c{0, 0, 0, true};
     if (a.kind == kStCompact) {
         const uint4 h = *reinterpret_cast<const uint4*>(a.inst + i);  // {first_cmd, n_cmds, flags}
         if (!(h.w & MPX_IC_HAS_CMDS)) return r;
-        lo = (uint64_t)h.x | ((uint64_t)h.y << 32), len = h.z;
+        uint64_t lo = (uint64_t)h.x | ((uint64_t)h.y << 32), len = h.z;
         uint64_t bound = *a.from_used;
         bound = bound < S[0].n_cmds ? bound : S[0].n_cmds;
         if (lo > bound || len > bound - lo || len == kStNone) ebits |= kErrInval, lo = 0, len = 0;
@@ -134,59 +108,28 @@ __device__ __forceinline__ StItem st_item(const StArgs& a, const StSrc* S, uint6
         const uint4 m = *(reinterpret_cast<const uint4*>(a.items) + i);  // {instance, ballot, leader, value}
         if (!(a.effect[i] & a.store_mask) || m.w == MPX_VALUE_KEEP) return r;
         r.instance = (int32_t)m.x;
-        const uint64_t p = a.perm ? a.perm[i] : i;
-        if (p >= a.n_recs) {
-            ebits |= kErrInval;
-            return r;
-        }
-        while (sid + 1 < a.n_src && p >= S[sid].rec_end) ++sid;
-        if (m.w >= S[sid].n_frames) {
-            ebits |= kErrInval;
-            return r;
-        }
-        lo = S[sid].cmd_off[m.w];
-        const uint64_t hi = S[sid].cmd_off[m.w + 1];
-        if (hi < lo || hi > S[sid].n_cmds || hi - lo >= kStNone) {
-            ebits |= kErrInval;
-            return r;
-        }
-        len = hi - lo;
+        c = msg_cmds(S, a.n_src, a.n_recs, a.perm, i, m.w, ebits);
     } else {
         const uint4* x = reinterpret_cast<const uint4*>(a.items) + 2 * i;
-        const uint4 h = x[0], c = x[1];  // {instance, ballot, last_committed, flags} {first_cmd, n_cmds, pad}
+        const uint4 h = x[0], f = x[1];  // {instance, ballot, last_committed, flags} {first_cmd, n_cmds, pad}
         if (!(h.w & (MPX_PH_ACCEPT | MPX_PH_PREPARE))) return r;
         r.instance = (int32_t)h.x;
-        lo = (uint64_t)c.x | ((uint64_t)c.y << 32), len = c.z;
-        if (lo > S[0].n_cmds || len > S[0].n_cmds - lo || len == kStNone) {
-            ebits |= kErrInval;
-            return r;
-        }
+        c = send_cmds(S[0], (uint64_t)f.x | ((uint64_t)f.y << 32), f.z, ebits);
     }
+    if (!c.ok) return r;
     const int64_t rel = (int64_t)r.instance - a.inst_base;
     if (rel < 0 || (uint64_t)rel >= a.n_inst) {
         ebits |= kErrNil;
         return r;
     }
-    r.len = (uint32_t)len, r.pos = (sid << 56) | lo;
+    r.len = (uint32_t)c.len, r.pos = cmd_pos(c.src, c.lo);
     return r;
-}
-
-// the entry of output position p, given off(l) <= p < off(h): the last one that starts at or
-// before p (the empty ones before it start there too and are passed over)
-template <typename Acc>
-__device__ __forceinline__ uint32_t st_entry_of(const Acc& acc, uint64_t p, uint32_t l, uint32_t h) {
-    while (h - l > 1) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (acc.off(mid) <= p) l = mid;
-        else h = mid;
-    }
-    return l;
 }
 
 // Arena positions q0 .. q0 + 3 (q0 a multiple of 4): those inside [first, first + total) take the
 // call's output positions q - first, whose entries lie in [e_lo, e_hi].
 template <typename Acc>
-__device__ __forceinline__ void st_emit4(const StArgs& a, const StSrc* S, const Acc& acc, uint64_t q0,
+__device__ __forceinline__ void st_emit4(const StArgs& a, const CmdSrc* S, const Acc& acc, uint64_t q0,
                                          uint64_t first, uint64_t total, uint32_t e_lo, uint32_t e_hi) {
     uint32_t o[kStPer];
     uint64_t k[kStPer], v[kStPer];
@@ -204,12 +147,12 @@ __device__ __forceinline__ void st_emit4(const StArgs& a, const StSrc* S, const 
         if (in[j]) {
             const uint64_t p = q - first;
             if (!started || p >= end) {
-                e = st_entry_of(acc, p, started ? e + 1 : e_lo, e_hi + 1);
+                e = last_at_or_before([&](uint32_t x) { return acc.off(x); }, p, started ? e + 1 : e_lo, e_hi + 1);
                 begin = acc.off(e), end = acc.off(e + 1);
                 const uint64_t pos = acc.pos(e);
-                const StSrc& s = S[pos >> 56];
+                const CmdSrc& s = S[cmd_pos_src(pos)];
                 s_op = s.op, s_key = s.key, s_val = s.val;
-                from = pos & ((1ull << 56) - 1);
+                from = cmd_pos_lo(pos);
                 started = true;
             }
             const uint64_t src = from + (p - begin);
@@ -219,37 +162,7 @@ __device__ __forceinline__ void st_emit4(const StArgs& a, const StSrc* S, const 
             any = true;
         }
     }
-    if (!any) return;
-    uint8_t* const d_op = a.a_op + q0;
-    int64_t *const d_key = a.a_key + q0, *const d_val = a.a_val + q0;
-    if (in[0] && in[kStPer - 1]) {
-        // q0 is a multiple of 4: the four keys start 0 or 8 bytes into a 16-byte line with the array
-        const auto four = [](int64_t* d, const uint64_t (&x)[kStPer]) {
-            if (((uintptr_t)d & 15) == 0) {
-                reinterpret_cast<uint4*>(d)[0] =
-                    make_uint4((uint32_t)x[0], (uint32_t)(x[0] >> 32), (uint32_t)x[1], (uint32_t)(x[1] >> 32));
-                reinterpret_cast<uint4*>(d)[1] =
-                    make_uint4((uint32_t)x[2], (uint32_t)(x[2] >> 32), (uint32_t)x[3], (uint32_t)(x[3] >> 32));
-            } else {
-                d[0] = (int64_t)x[0];
-                *reinterpret_cast<uint4*>(d + 1) =
-                    make_uint4((uint32_t)x[1], (uint32_t)(x[1] >> 32), (uint32_t)x[2], (uint32_t)(x[2] >> 32));
-                d[3] = (int64_t)x[3];
-            }
-        };
-        four(d_key, k);
-        four(d_val, v);
-        if (((uintptr_t)d_op & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(d_op) = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kStPer; ++j) d_op[j] = (uint8_t)o[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kStPer; ++j)
-            if (in[j]) d_op[j] = (uint8_t)o[j], d_key[j] = (int64_t)k[j], d_val[j] = (int64_t)v[j];
-    }
+    if (any) store4_cmds(a.a_op + q0, a.a_key + q0, a.a_val + q0, o, k, v, in);
 }
 
 // whether the arena takes `total` more commands after `used0` (a cursor past cap is an error)
@@ -312,13 +225,13 @@ struct StAccLds {
 __global__ __launch_bounds__(kStT) void k_st_mark(StArgs a, uint32_t* __restrict__ st,
                                                   uint64_t* __restrict__ pos, uint64_t* __restrict__ words,
                                                   uint32_t* __restrict__ part) {
-    __shared__ StSrc S[MPX_SC_MAX_SRC];
-    st_sources(a, S);
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
+    cmd_sources(a.src, a.n_src, S);
     const uint64_t i = (uint64_t)blockIdx.x * kStT + threadIdx.x;
     uint32_t ebits = 0;
-    const StItem x = st_item(a, S, i, st_n_eff(a), ebits);
+    const StItem x = st_item(a, S, i, n_eff(a.d_n, a.n), ebits);
     if (i < a.n) st[i] = x.len, pos[i] = x.pos;
-    st_raise(a.err, ebits);
+    raise_bits(a.err, ebits, kErrInval | kErrNil);
     if (a.kind != kStCompact) return;  // (the same in every thread)
     // compaction: every flagged slot is a winner, entry k is slot k, the target starts at 0
     const uint32_t c = (uint32_t)__syncthreads_count(x.len != kStNone);
@@ -353,9 +266,9 @@ __global__ __launch_bounds__(kStT) void k_st_copy(StArgs a, const uint32_t* __re
                                                   const uint64_t* __restrict__ off,
                                                   const uint64_t* __restrict__ words,
                                                   const uint32_t* __restrict__ part, uint32_t n_part) {
-    __shared__ StSrc S[MPX_SC_MAX_SRC];
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
     __shared__ uint64_t ws[kStT / kWave];
-    st_sources(a, S);
+    cmd_sources(a.src, a.n_src, S);
     const uint32_t t = threadIdx.x;
     const uint64_t total = off[a.n], ns = words[0], used0 = words[1];
     bool bad;
@@ -380,13 +293,8 @@ __global__ __launch_bounds__(kStT) void k_st_copy(StArgs a, const uint32_t* __re
     if (blockIdx.x) return;
     uint64_t won = 0;
     for (uint32_t x = t; x < n_part; x += kStT) won += part[x];
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) won += shfl_any(won, lane_id() ^ d);
-    if (lane_id() == 0) ws[t / kWave] = won;
-    __syncthreads();
+    won = block_sum<uint64_t, kStT>(won, ws);
     if (t == 0) {
-        won = 0;
-        for (int w = 0; w < kStT / kWave; ++w) won += ws[w];
         a.res->n_stored = won;
         a.res->n_cmds = total;
         a.res->n_superseded = a.kind == kStCompact ? 0 : ns - won;
@@ -398,19 +306,21 @@ __global__ __launch_bounds__(kStT) void k_st_copy(StArgs a, const uint32_t* __re
 
 // ---- one launch: a replica-sized batch in one workgroup, no scratch ------------------------------
 __global__ __launch_bounds__(kStOneT) void k_st_one(StArgs a) {
-    __shared__ StSrc S[MPX_SC_MAX_SRC];
+    __shared__ CmdSrc S[MPX_SC_MAX_SRC];
     __shared__ uint32_t c_len[kStOneT];
     __shared__ int32_t c_inst[kStOneT];
     __shared__ uint64_t c_pos[kStOneT], s_off[kStOneT + 1];
     __shared__ uint64_t ws[kStOneT / kWave];
-    st_sources(a, S);
+    cmd_sources(a.src, a.n_src, S);
     const uint32_t t = threadIdx.x;
     const uint64_t used0 = *a.used;
     uint32_t ebits = 0;
-    const StItem x = st_item(a, S, t, st_n_eff(a), ebits);
-    st_raise(a.err, ebits);
+    const StItem x = st_item(a, S, t, n_eff(a.d_n, a.n), ebits);
+    raise_bits(a.err, ebits, kErrInval | kErrNil);
     // the storing items' list
     const uint32_t flag = x.len != kStNone;
+    // (not assemble.hpp's block_excl_scan: one fixed-trip select gives the prefix and the total from
+    // four 16-byte LDS reads; the helper's loop to the thread's own wave read 0.2 us slower here)
     const uint32_t incl = wave_incl_scan(flag, ScanSum32{});
     if (lane_id() == kWave - 1) ws[t / kWave] = incl;
     __syncthreads();
@@ -427,14 +337,9 @@ __global__ __launch_bounds__(kStOneT) void k_st_one(StArgs a) {
     // the winners and their offsets
     const bool win = t < ns && (t + 1 >= ns || c_inst[t + 1] != c_inst[t]);
     const uint32_t len = win ? c_len[t] : 0u;
-    const uint64_t inc2 = wave_incl_scan((uint64_t)len, ScanSum64{});
-    if (lane_id() == kWave - 1) ws[t / kWave] = inc2;
-    const uint32_t won = (uint32_t)__syncthreads_count(win);
-    uint64_t bef2 = 0;
-    for (uint32_t w = 0; w < t / kWave; ++w) bef2 += ws[w];
-    s_off[t + 1] = bef2 + inc2;
+    s_off[t + 1] = block_excl_scan<uint64_t, kStOneT>((uint64_t)len, ws) + len;
     if (t == 0) s_off[0] = 0;
-    __syncthreads();
+    const uint32_t won = (uint32_t)__syncthreads_count(win);
     const uint64_t total = s_off[kStOneT];
     bool bad;
     const bool full = st_full(a, used0, total, bad);
@@ -499,13 +404,8 @@ hipError_t launch_store_commands(const mpx_store_batch* b, const mpx_store_arena
     a.a_op = arena->op, a.a_key = arena->key, a.a_val = arena->val, a.used = arena->used;
     a.inst = inst, a.res = res, a.err = err;
     a.inst_base = b->inst_base, a.kind = b->kind, a.n_src = (uint32_t)b->n_src, a.store_mask = b->store_mask;
-    uint64_t recs = 0, cmds = 0;
-    for (size_t s = 0; s < b->n_src; ++s) {
-        const mpx_store_src& x = b->src[s];
-        recs += x.n_recs, cmds += x.n_cmds;
-        a.src[s] = StSrc{x.cmd_off, x.op, x.key, x.val, x.n_frames, x.n_cmds, recs};
-    }
-    a.n_recs = recs;
+    uint64_t cmds;
+    fill_cmd_sources(b->src, b->n_src, a.src, a.n_recs, cmds);
     if (!(b->flags & MPX_SC_GENERAL) && n <= MPX_SC_ONE_LAUNCH_ITEMS && cmds <= MPX_SC_ONE_LAUNCH_CMDS) {
         k_st_one<<<1, kStOneT, 0, stream>>>(a);
         return hipGetLastError();
@@ -544,7 +444,7 @@ hipError_t launch_store_compact(mpx_inst_cmds* inst, uint64_t n_inst, const mpx_
     a.a_op = to->op, a.a_key = to->key, a.a_val = to->val, a.used = to->used;
     a.inst = inst, a.res = res, a.err = err;
     a.kind = kStCompact, a.n_src = 1;
-    a.src[0] = StSrc{nullptr, from->op, from->key, from->val, 0, from->cap, 0};
+    a.src[0] = CmdSrc{nullptr, from->op, from->key, from->val, 0, from->cap, 0};
     Carver c(work);
     const StWork w(c, n_inst);
     if (work_bytes < c.bytes()) return hipErrorInvalidValue;

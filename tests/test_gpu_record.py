@@ -659,3 +659,98 @@ def test_graph_of_a_followers_accepts_to_their_records(mk_engine, general):
             e.graph_destroy(gr)
             e.stream_destroy(s)
         e.synchronize()
+
+
+# ---- store assembly and record assembly resolve one batch alike ------------------------------------
+def _shared_batch(faulty=False):
+    """300 Commits over three connections of 100 records each, merged by a perm that is no identity
+    and grouped by instance in runs of one or two; record r of a connection is its frame r. One
+    item is a CommitShort (MPX_VALUE_KEEP), some carry no MPX_CH_CMDS, some name an empty frame.
+    faulty: one storing item names frame n_frames of its source."""
+    import store_translit as ST
+    rng = np.random.default_rng(2024)
+    n, per, base = 300, 100, 40
+    sizes = rng.choice([0, 1, 2, 3], (3, per), p=[0.2, 0.4, 0.25, 0.15])
+    sources = [T.mk_source(sizes[s].tolist(), seed=40 + s, gap=s) for s in range(3)]
+    perm = rng.permutation(n).astype(np.uint32)
+    instance = base + np.cumsum(rng.random(n) < 0.6)            # ascending, runs of equal instances
+    value = (perm % per).astype(np.int64)
+    eff = np.where(rng.random(n) < 0.85, R.CH_CMDS | R.CH_INSTALLED, R.CH_INSTALLED).astype(np.uint8)
+    at_end, at_last = int(np.flatnonzero(perm == per)[0]), int(np.flatnonzero(perm == n - 1)[0])
+    keep = next(i for i in range(n) if i not in (at_end, at_last))
+    value[keep] = R.VALUE_KEEP
+    eff[[at_end, at_last, keep]] |= R.CH_CMDS
+    if faulty:
+        value[next(i for i in range(n) if eff[i] & R.CH_CMDS and i != keep)] = per
+    items = T.mk_msgs([(int(instance[i]), 9, int(value[i])) for i in range(n)])
+    n_inst = int(instance[-1]) - base + 2
+    record = dict(kind=R.LR_COMMITS, fmt=R.LOG_DURABLE, items=items, sources=sources, effect=eff, perm=perm)
+    total = int(sizes.sum())
+    store = dict(kind=R.SC_MSGS, items=items, sources=sources, effect=eff, perm=perm, store_mask=R.CH_CMDS,
+                 handler="commit", arena=ST.mk_arena(5 + total, 6), used=5, inst_base=base,
+                 inst=ST.mk_window(n_inst, 5, 0.3, np.random.default_rng(7)))
+    storing = [i for i in range(n) if eff[i] & R.CH_CMDS and value[i] != R.VALUE_KEEP]
+    winners = [i for k, i in enumerate(storing)
+               if k + 1 == len(storing) or instance[storing[k + 1]] != instance[i]]
+    if not faulty:
+        assert not np.array_equal(perm, np.arange(n)) and len(winners) < len(storing) < n - 1
+        assert at_end in storing and at_last in storing
+        assert any(sizes[perm[i] // per, perm[i] % per] == 0 for i in winners)
+    return store, record, winners
+
+
+def _stored_equals_recorded(store, got_s, got_r, winners):
+    """every winner's slot names as many commands as its record holds past the 12 metadata bytes,
+    and the arena holds the commands the record bytes hold"""
+    cmd = np.dtype([("op", "u1"), ("key", "<i8"), ("val", "<i8")])
+    assert cmd.itemsize == 17
+    for i in winners:
+        slot = got_s["inst"][int(store["items"]["instance"][i]) - store["inst_base"]]
+        lo, hi = int(got_r["item_off"][i]), int(got_r["item_off"][i + 1])
+        k, first = int(slot["n_cmds"]), int(slot["first_cmd"])
+        assert int(slot["flags"]) == R.IC_HAS_CMDS and k == (hi - lo - 12) // 17 and (hi - lo - 12) % 17 == 0, i
+        rec = np.frombuffer(got_r["out"][lo + 12:hi].tobytes(), cmd)
+        assert np.array_equal(rec["op"], got_s["op"][first:first + k]), i
+        assert np.array_equal(rec["key"], got_s["key"][first:first + k]), i
+        assert np.array_equal(rec["val"], got_s["val"][first:first + k]), i
+
+
+@pytest.mark.gpu
+def test_store_and_record_resolve_one_batch_alike(eng):
+    """one MPX_SC_MSGS / MPX_LR_COMMITS batch through both calls, on the one-launch path and on the
+    general path (300 items: two workgroups of the item pass): a perm entry equal to a source's
+    rec_end, the last record of the last source, an empty frame and a CommitShort among the items"""
+    import store_translit as ST
+    import test_gpu_store as TS
+    store, record, winners = _shared_batch()
+    want_s, want_r = ST.store_commands(**store), want_of(record)
+    assert want_s["code"] == R.OK and want_r["code"] == R.OK
+    assert int(want_s["res"]["n_stored"]) == len(winners)
+    _stored_equals_recorded(store, want_s, want_r, winners)
+    for general in (False, True):
+        got_s, code_s = TS.run_dev(eng, store, general, op_shift=1, kv_shift=8)
+        got_r, code_r = run_dev(eng, record, general, out_shift=3)
+        assert code_s == R.OK and code_r == R.OK
+        TS.same(got_s, want_s, f"store general={general}")
+        same(got_r, want_r, f"record general={general}")
+        _stored_equals_recorded(store, got_s, got_r, winners)
+        TS.same(TS.run_host(eng, store, general), want_s, f"store host general={general}")
+        same(run_host(eng, record, general), want_r, f"record host general={general}")
+
+
+@pytest.mark.gpu
+def test_store_and_record_refuse_one_faulty_item_alike(eng):
+    """value_id == n_frames of the item's source: both calls answer the same code, by the error word
+    and before any launch, on both paths"""
+    import store_translit as ST
+    import test_gpu_store as TS
+    store, record, _ = _shared_batch(faulty=True)
+    want_s, want_r = ST.store_commands(**dict(store, dev=True)), want_of(record, dev=True)
+    assert want_s["code"] == want_r["code"] == R.E_INVAL
+    for general in (False, True):
+        got_s, code_s = TS.run_dev(eng, store, general)
+        got_r, code_r = run_dev(eng, record, general)
+        assert code_s == code_r == R.E_INVAL
+        TS.same(got_s, want_s, f"store general={general}")
+        same(got_r, want_r, f"record general={general}")
+        assert _code(TS.run_host, eng, store, general) == _code(run_host, eng, record, general) == R.E_INVAL
