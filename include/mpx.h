@@ -36,7 +36,9 @@
  *   mpx_propose_handle    <- bareminpaxos.(*Replica).handlePropose  bareminpaxos.go:617-710 /
  *                            paxos.(*Replica).handlePropose  src/paxos/paxos.go:388-443: which
  *                            drained proposals become an instance, and mpx_encode_accepts the
- *                            Accept frames bcastAccept (:450-520 / :299-331) writes to every peer
+ *                            Accept frames bcastAccept (:450-520 / :299-331) writes to every peer;
+ *                            mpx_encode_accepts_stored the same frames with the CatchUpLog read
+ *                            from the instance store (st / lb / mpx_inst_cmds and the arena)
  *   mpx_unmarshal_frames  <- Accept / Commit / PrepareReply.Unmarshal with Instance.Unmarshal and
  *                            Command.Unmarshal (minpaxosprotomarsh.go:470-507, :648-672, :352-387,
  *                            :126-153 / paxosprotomarsh.go:244-268, :403-430, :152-176;
@@ -141,7 +143,8 @@ extern "C" {
                               mpx_build_replies[_reserve|_dev],
                               mpx_execute_gather[_reserve|_dev],
                               mpx_store_commands[_reserve|_dev], mpx_store_compact[_reserve|_dev],
-                              mpx_record_log[_reserve|_dev], mpx_record_bound */
+                              mpx_record_log[_reserve|_dev], mpx_record_bound,
+                              mpx_encode_accepts_stored[_reserve|_dev] */
 
 /* ---- error codes ---------------------------------------------------------------------- */
 #define MPX_OK 0
@@ -1766,6 +1769,74 @@ int mpx_record_log_reserve(mpx_engine* eng, size_t max_n);
  * MPX_E_INVAL.                                                                                 */
 int mpx_record_log_dev(mpx_engine* eng, const mpx_record_batch* b, uint8_t* d_out, size_t out_cap,
                        uint64_t* d_item_off, mpx_record_result* d_res, void* stream);
+
+/* ---- Accept frames with the catch-up log read from the instance store ---------------------------
+ * A second form of mpx_encode_accepts for a leader that keeps its instances on the device: the
+ * CatchUpLog of a MIN frame is not a dense window-ordered copy (log_recs / log_cmd_off / log_*)
+ * but the state the handlers and mpx_store_commands already maintain. Every field mpx_accept_batch
+ * shares with this struct means what it means there; frames, destinations, dest_off, the out_cap
+ * rule, the rules about last_committed and the CLASSIC wire are mpx_encode_accepts' word for word,
+ * and so are the bytes whenever the dense log describes the same instances.
+ * Log record i (window index), Instance.Marshal (minpaxosprotomarsh.go:100-124):
+ *   nil      exactly when st[i].status == MPX_STATUS_NIL
+ *   Ballot   st[i].ballot
+ *   Status   lb[i].status where lb is given and lb[i].status != MPX_STATUS_NIL, else st[i].status
+ *            (the Go keeps one Status per instance; here mpx_propose_handle writes PREPARED into
+ *            both windows, mpx_accept_tally moves only lb to COMMITTED, and the acceptor and commit
+ *            handlers write only st)
+ *   Cmds     with inst[i].flags & MPX_IC_HAS_CMDS: src[first_cmd .. first_cmd + n_cmds); without
+ *            it Cmds == nil, which marshals as V(0) (:117-123) - an instance a CommitShort made
+ *            is this case, and it is legal
+ * The arena is named and bounded as mpx_execute_batch names it (n_src = its capacity). CLASSIC
+ * frames carry no log: st / lb / inst / src_* are not read and may be null.
+ * Errors, host form, answered before anything is staged: everything mpx_encode_accepts answers,
+ * with the same codes; reserved != 0, or null st / inst with MIN sends -> MPX_E_INVAL; a nil
+ * instance inside some destination's catch-up range -> MPX_E_NIL_INSTANCE; a flagged slot inside a
+ * range whose [first_cmd, first_cmd + n_cmds) leaves [0, n_src) -> MPX_E_INVAL. Slots outside
+ * every range are not judged. The host form stages the span of st / lb / inst between the lowest
+ * and the highest window index any range touches and, of the arena, only the commands of the
+ * instances inside some range, gathered into a compact copy (never the arena itself).            */
+typedef struct mpx_accept_store_batch {
+    const mpx_accept_send* sends;
+    size_t n_sends;
+    int32_t inst_base;
+    uint32_t ipg;
+    size_t n_groups;
+    const mpx_proposer_group* groups;
+    const int32_t* peer_commits;
+    const uint8_t* cmd_op;         /* the sends' new commands, as mpx_accept_batch.cmd_*         */
+    const int64_t* cmd_key;
+    const int64_t* cmd_val;
+    size_t n_cmds;
+    const mpx_acceptor_state* st;  /* n_inst: ballot and status of instanceSpace[i]              */
+    const mpx_inst_state* lb;      /* n_inst, optional: the leader bookkeeping window            */
+    const mpx_inst_cmds* inst;     /* n_inst: where the slot's Cmds live                         */
+    const uint8_t* src_op;         /* the command arena, n_src                                   */
+    const int64_t* src_key;
+    const int64_t* src_val;
+    size_t n_src;
+    uint32_t flags;                /* MPX_AB_*                                                   */
+    uint32_t alive_mask;
+    uint32_t reserved;             /* 0                                                          */
+} mpx_accept_store_batch;
+
+int mpx_encode_accepts_stored(mpx_engine* eng, const mpx_accept_store_batch* b, uint8_t* out,
+                              size_t out_cap, uint64_t* dest_off);
+/* scratch for _dev calls of up to max_sends slots over a window of up to max_n_inst instances
+ * (grows only). It is the scratch of mpx_encode_accepts_dev, sized for this form's one more array:
+ * both forms of one handle run in one stream order, and a larger reserve of either invalidates
+ * graphs captured before it.                                                                    */
+int mpx_encode_accepts_stored_reserve(mpx_engine* eng, size_t max_sends, size_t max_n_inst);
+/* device form: b is a host struct of device pointers. Needs mpx_encode_accepts_stored_reserve
+ * first. Never allocates or synchronises, needs no memset on the stream; it captures into a graph.
+ * What mpx_encode_accepts_dev reports through the error word it reports alike; a nil instance
+ * inside a catch-up range (MPX_E_NIL_INSTANCE) and a flagged slot inside one whose range leaves
+ * the arena (MPX_E_INVAL) arrive the same way, and such an instance is sized and encoded as having
+ * no commands: frame sizes and bytes agree and no load leaves [0, n_src). Alignment: sends,
+ * groups, st, lb, inst 16 bytes; cmd_key, cmd_val, src_key, src_val and d_dest_off 8; peer_commits
+ * 4; cmd_op, src_op and d_out any address; any other address is rejected with MPX_E_INVAL.     */
+int mpx_encode_accepts_stored_dev(mpx_engine* eng, const mpx_accept_store_batch* b, uint8_t* d_out,
+                                  size_t out_cap, uint64_t* d_dest_off, void* stream);
 
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:

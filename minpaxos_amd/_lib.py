@@ -45,6 +45,14 @@ class MpxAcceptBatch(C.Structure):
                 ("n_log_cmds", _sz), ("flags", C.c_uint32), ("alive_mask", C.c_uint32)]
 
 
+class MpxAcceptStoreBatch(C.Structure):
+    _fields_ = [("sends", _p), ("n_sends", _sz), ("inst_base", C.c_int32), ("ipg", C.c_uint32),
+                ("n_groups", _sz), ("groups", _p), ("peer_commits", _p), ("cmd_op", _p),
+                ("cmd_key", _p), ("cmd_val", _p), ("n_cmds", _sz), ("st", _p), ("lb", _p),
+                ("inst", _p), ("src_op", _p), ("src_key", _p), ("src_val", _p), ("n_src", _sz),
+                ("flags", C.c_uint32), ("alive_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MpxUnmarshalOut(C.Structure):
     _fields_ = [("accepts", _p), ("accept_last_committed", _p), ("accept_cap", _sz),
                 ("commits", _p), ("commit_cap", _sz), ("cmd_off", _p), ("op", _p), ("key", _p),
@@ -198,6 +206,10 @@ SIGNATURES = {
     "mpx_encode_accepts": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p]),
     "mpx_encode_accepts_reserve": (C.c_int, [_p, _sz, _sz, _sz]),
     "mpx_encode_accepts_dev": (C.c_int, [_p, C.POINTER(MpxAcceptBatch), _p, _sz, _p, _p]),
+    "mpx_encode_accepts_stored": (C.c_int, [_p, C.POINTER(MpxAcceptStoreBatch), _p, _sz, _p]),
+    "mpx_encode_accepts_stored_reserve": (C.c_int, [_p, _sz, _sz]),
+    "mpx_encode_accepts_stored_dev": (C.c_int, [_p, C.POINTER(MpxAcceptStoreBatch), _p, _sz, _p,
+                                                _p]),
     "mpx_unmarshal_frames": (C.c_int, [_p, _p, _sz, _p, _sz, C.POINTER(MpxUnmarshalOut), _p]),
     "mpx_unmarshal_frames_reserve": (C.c_int, [_p, _sz, _sz]),
     "mpx_unmarshal_frames_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, C.POINTER(MpxUnmarshalOut),

@@ -1143,12 +1143,6 @@ int mpx_encode_accept_replies(mpx_engine* e, const mpx_accept_reply* replies,
 
 // ---- the proposer side: handlePropose and the Accept bytes -----------------------------------
 namespace {
-int propose_shape(mpx_engine* e, size_t n_groups, size_t n_inst, uint32_t ipg) {
-    if (n_groups > (1ull << 32) || n_inst > (1ull << 32) ||
-        (n_groups ? (!ipg || n_groups * (uint64_t)ipg != n_inst) : n_inst != 0))
-        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
-    return MPX_OK;
-}
 // what the host and _dev forms of the Accept encoder check alike
 int accept_batch_args(mpx_engine* e, const mpx_accept_batch* b, const void* out, size_t out_cap,
                       const void* dest_off) {
@@ -1162,22 +1156,6 @@ int accept_batch_args(mpx_engine* e, const mpx_accept_batch* b, const void* out,
         (!b->peer_commits || !b->log_recs || !b->log_cmd_off))
         return fail(e, MPX_E_INVAL, "MIN needs peer_commits and the log");
     return MPX_OK;
-}
-
-// bcastAccept's ring walk from self (bareminpaxos.go:465-482 / paxos.go:312-327): bit q set when
-// q receives the Accept
-uint32_t accept_dests(int mode, int32_t N, int32_t self, bool thrifty, uint32_t alive) {
-    const int n = thrifty ? N >> 1 : N - 1;
-    uint32_t m = 0;
-    int32_t q = self;
-    for (int sent = 0; sent < n;) {
-        q = (q + 1) % N;
-        if (q == self) break;
-        if (mode != MPX_MODE_MIN && !((alive >> q) & 1u)) continue;
-        ++sent;
-        m |= 1u << q;
-    }
-    return m;
 }
 }  // namespace
 

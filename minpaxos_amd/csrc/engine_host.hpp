@@ -1,5 +1,6 @@
 // engine_host.hpp — the host side's private parts that more than one translation unit of the
-// C-ABI layer needs (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp, store.cpp, record.cpp): the handle,
+// C-ABI layer needs (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp, store.cpp, record.cpp,
+// accepts_stored.cpp): the handle,
 // error reporting, the families' scratch buffers and the staging arena of the host-pointer forms.
 // The command sources of store.cpp and record.cpp (their checks, the pre-check of an item's
 // commands, their staging) are cmd_src_host.hpp's, the host side of the kernels' assemble.hpp.
@@ -199,6 +200,30 @@ inline int reserved(mpx_engine* e, const DevBuf& work, uint64_t need, const char
     if (work.cap >= need) return MPX_OK;
     return fail(e, MPX_E_INVAL, std::string(entry) + ": call " + reserve_call +
                                     " first (the dev entry point never allocates)");
+}
+
+// ---- what the two forms of the Accept encoder share (engine.cpp, accepts_stored.cpp) ----------
+inline int propose_shape(mpx_engine* e, size_t n_groups, size_t n_inst, uint32_t ipg) {
+    if (n_groups > (1ull << 32) || n_inst > (1ull << 32) ||
+        (n_groups ? (!ipg || n_groups * (uint64_t)ipg != n_inst) : n_inst != 0))
+        return fail(e, MPX_E_INVAL, "n_inst must equal n_groups * ipg (at most 2^32)");
+    return MPX_OK;
+}
+
+// bcastAccept's ring walk from self (bareminpaxos.go:465-482 / paxos.go:312-327): bit q set when
+// q receives the Accept
+inline uint32_t accept_dests(int mode, int32_t N, int32_t self, bool thrifty, uint32_t alive) {
+    const int n = thrifty ? N >> 1 : N - 1;
+    uint32_t m = 0;
+    int32_t q = self;
+    for (int sent = 0; sent < n;) {
+        q = (q + 1) % N;
+        if (q == self) break;
+        if (mode != MPX_MODE_MIN && !((alive >> q) & 1u)) continue;
+        ++sent;
+        m |= 1u << q;
+    }
+    return m;
 }
 
 }  // namespace mpx_host

@@ -213,6 +213,15 @@ uint64_t accepts_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst,
 hipError_t launch_encode_accepts(
     int mode, int32_t nrep, const mpx_accept_batch* b, uint8_t* out, uint64_t out_cap,
     uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+// ... with the catch-up log read from the instance store (mpx_encode_accepts_stored;
+// accepts_stored.hip). Its scratch holds the dense encoder's regions and the synthetic command
+// offsets, so it is never smaller than accepts_work_bytes of the same sizes; a CLASSIC call is
+// launch_encode_accepts on the same scratch.
+uint64_t accepts_stored_work_bytes(uint32_t nrep, uint64_t n_sends, uint64_t n_inst,
+                                   Carver&& c = Carver());
+hipError_t launch_encode_accepts_stored(
+    int mode, int32_t nrep, const mpx_accept_store_batch* b, uint8_t* out, uint64_t out_cap,
+    uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
 // ---- Accept / Commit / PrepareReply payloads (mpx_unmarshal_frames; unmarshal.hip) ----------
 // Scratch for calls of up to n_var frames carrying up to n_log catch-up instances in total.

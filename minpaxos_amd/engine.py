@@ -14,6 +14,7 @@ Names and argument meaning follow the reference handlers they replace:
   encode_accept_replies <- replyAccept -> SendMsg: the AcceptReply frames per leader connection
   propose_handle      <- bareminpaxos / paxos  handlePropose (which proposals become an instance)
   encode_accepts      <- bcastAccept -> SendMsg: the Accept frames per peer connection
+  encode_accepts_stored  the same frames, the catch-up log read from the instance store
   unmarshal_frames    <- Accept / Commit / PrepareReply.Unmarshal (+ Instance, Command) of the
                          frames decode_stream found: records and SoA arrays
   commit_handle       <- bareminpaxos / paxos  handleCommit, handleCommitShort and
@@ -554,6 +555,72 @@ class Engine:
         self._check(self.lib.mpx_encode_accepts_dev(self.h, C.byref(batch), d_out, out_cap,
                                                     d_dest_off, stream),
                     "mpx_encode_accepts_dev")
+
+    def encode_accepts_stored(self, sends, groups, cmds, inst_base=0, ipg=None, peer_commits=None,
+                              st=None, lb=None, inst=None, arena=None, thrifty=False,
+                              alive_mask=0xFFFF, out_cap=None):
+        """encode_accepts with the catch-up log read from the instance store: st ACCEPTOR_STATE
+        [n_inst] (ballot, status), lb optional INST_STATE[n_inst] (its non-nil status wins), inst
+        INST_CMDS[n_inst] and arena (op, key, val) they point into (MIN; CLASSIC reads none of
+        them). Returns (bytes uint8, dest_off u64[N+1]) like encode_accepts."""
+        sends = _c(sends, R.ACCEPT_SEND)
+        groups = _c(np.atleast_1d(groups), R.PROPOSER_GROUP)
+        op, key, val = _c(cmds[0], np.uint8), _c(cmds[1], np.int64), _c(cmds[2], np.int64)
+        G, N = len(groups), self.n_replicas
+        keep = [sends, groups, op, key, val]
+        b = _lib.MpxAcceptStoreBatch()
+        b.sends, b.n_sends, b.inst_base = _ptr(sends), len(sends), inst_base
+        b.groups, b.n_groups = _ptr(groups), G
+        b.cmd_op, b.cmd_key, b.cmd_val, b.n_cmds = _ptr(op), _ptr(key), _ptr(val), len(op)
+        b.flags = R.AB_THRIFTY if thrifty else 0
+        b.alive_mask = alive_mask
+        n_inst = 0
+        if st is not None:
+            st = _c(st, R.ACCEPTOR_STATE)
+            keep.append(st)
+            n_inst, b.st = len(st), _ptr(st)
+        if lb is not None:
+            lb = _c(lb, R.INST_STATE)
+            keep.append(lb)
+            b.lb = _ptr(lb)
+        if inst is not None:
+            inst = _c(inst, R.INST_CMDS)
+            keep.append(inst)
+            b.inst = _ptr(inst)
+        if arena is not None:
+            sop, skey, sval = _c(arena[0], np.uint8), _c(arena[1], np.int64), _c(arena[2], np.int64)
+            keep += [sop, skey, sval]
+            b.src_op, b.src_key, b.src_val, b.n_src = _ptr(sop), _ptr(skey), _ptr(sval), len(sop)
+        if peer_commits is not None:
+            pc = _c(peer_commits, np.int32)
+            keep.append(pc)
+            b.peer_commits = _ptr(pc)
+        if ipg is None and st is None:
+            raise ValueError("encode_accepts_stored: ipg is needed when no st gives the window's size")
+        b.ipg = (n_inst // G if G else 0) if ipg is None else ipg
+        if out_cap is None:  # every frame with its group's largest possible catch-up log
+            sel = sends[(sends["flags"] & R.PH_ACCEPT) != 0]
+            logb = 0
+            if inst is not None and n_inst and G:
+                k = np.where(inst["flags"] & R.IC_HAS_CMDS, inst["n_cmds"], 0).astype(np.int64)
+                logb = 18 * b.ipg + 17 * int(k.reshape(G, -1).sum(axis=1).max())
+            out_cap = int((28 * len(sel) + 17 * int(sel["n_cmds"].sum()) + logb * len(sel)) * N)
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        off = np.zeros(N + 1, np.uint64)
+        rc = self.lib.mpx_encode_accepts_stored(self.h, C.byref(b), _ptr(out), out_cap, _ptr(off))
+        self._check(rc, "mpx_encode_accepts_stored")
+        del keep
+        return out[:int(off[-1])], off
+
+    def encode_accepts_stored_reserve(self, max_sends, max_n_inst):
+        self._check(self.lib.mpx_encode_accepts_stored_reserve(self.h, max_sends, max_n_inst),
+                    "mpx_encode_accepts_stored_reserve")
+
+    def encode_accepts_stored_dev(self, batch, d_out, out_cap, d_dest_off, stream=None):
+        """batch: _lib.MpxAcceptStoreBatch of device pointers"""
+        self._check(self.lib.mpx_encode_accepts_stored_dev(self.h, C.byref(batch), d_out, out_cap,
+                                                           d_dest_off, stream),
+                    "mpx_encode_accepts_stored_dev")
 
     # ---- Accept / Commit / PrepareReply payloads: Unmarshal in a batch -------------------------
     def unmarshal_frames(self, buf, var, caps=None):

@@ -114,6 +114,9 @@ ACCEPT_SEND = np.dtype([("instance", "<i4"), ("ballot", "<i4"), ("last_committed
 PROPOSE_MAX_BATCH = 5000
 PH_ACCEPT, PH_NOT_LEADER, PH_REFUSED, PH_PREPARE = 1, 2, 4, 8
 AB_THRIFTY = 1
+# mpx_encode_accepts_stored reads the catch-up log from the instance store instead of LOG_REC
+# arrays: ACCEPTOR_STATE (ballot, status), optionally INST_STATE (the status once the tally has
+# committed), INST_CMDS and the command arena they point into (below)
 
 # the commit side (mpx_commit_handle / mpx_encode_commits / mpx_gather_commit_shorts)
 VALUE_KEEP = 0xFFFFFFFF  # value_id of a CommitShort record (no Command; nil Cmds on a nil instance)

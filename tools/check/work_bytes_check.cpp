@@ -129,6 +129,10 @@ int main(int argc, char** argv) {
     family("execute (slots, 1000 groups)", S, true, SIZE_OF(execute_work_bytes, x, 1000));
     family("execute (2^20 slots, groups)", S, true, SIZE_OF(execute_work_bytes, 1 << 20, x));
     family("record (items)", S, true, SIZE_OF(record_work_bytes, x));
+    family("accepts stored (N = 5, sends, 2^16 slots)", S, true,
+           SIZE_OF(accepts_stored_work_bytes, 5, x, 1 << 16));
+    family("accepts stored (N = 16, 1000 sends, slots)", S, true,
+           SIZE_OF(accepts_stored_work_bytes, 16, 1000, x));
     for (const int32_t cap : {1, 8192, 1 << 20, 1 << 24, 1 << 25}) {
         char name[64];
         std::snprintf(name, sizeof(name), "replay (inst_cap %d)", cap);
