@@ -1838,6 +1838,164 @@ int mpx_encode_accepts_stored_reserve(mpx_engine* eng, size_t max_sends, size_t 
 int mpx_encode_accepts_stored_dev(mpx_engine* eng, const mpx_accept_store_batch* b, uint8_t* d_out,
                                   size_t out_cap, uint64_t* d_dest_off, void* stream);
 
+/* ---- the prepare side: batched handlePrepare and the PrepareReply bytes ----------------------
+ * The follower's half of Phase 1:
+ *   handlePrepare  bareminpaxos.go:712-751 (MIN) / paxos.go:445-468 (CLASSIC)
+ *   replyPrepare   through SendMsg (genericsmr.go:499-512) and PrepareReply.Marshal
+ *                  (minpaxosprotomarsh.go:308-350 / paxosprotomarsh.go:126-150)
+ * Prepare bytes in (mpx_gather_prepares behind mpx_decode_stream), PrepareReply bytes out
+ * (mpx_encode_prepare_replies), both on device buffers; what goes out is what mpx_decode_stream,
+ * mpx_unmarshal_frames and mpx_prepare_select[_min] consume on the leader. The leader's
+ * bcastPrepare and its prepareBookkeeping setup stay on the host. Instance numbers are window
+ * numbers as in mpx_accept_handle: idx = instance - inst_base belongs to group g = idx / ipg,
+ * n_inst == n_groups * ipg, first_g = inst_base + g * ipg plays the reference's instance 0 of
+ * group g and "nothing committed" is first_g - 1.                                               */
+
+/* one Prepare, either mode. minpaxosproto.Prepare{LeaderId,Ballot,LastCommitted}
+ * (minpaxosproto.go) / paxosproto.Prepare{LeaderId,Instance,Ballot,ToInfinity}.                */
+typedef struct mpx_prepare_msg {
+    int32_t key;       /* CLASSIC: Instance (window number). MIN: the group the connection
+                          belongs to, in [0, n_groups)                                          */
+    int32_t ballot;
+    int32_t leader_id;
+    int32_t arg;       /* CLASSIC: ToInfinity (the wire byte, 0..255). MIN: LastCommitted
+                          (window number)                                                        */
+} mpx_prepare_msg; /* 16 B */
+
+#define MPX_PRH_OK 1u     /* the reply's OK is TRUE                                              */
+#define MPX_PRH_RAISED 2u /* this message changed default_ballot                                 */
+#define MPX_PRH_LOG 4u    /* MIN: the catch-up branch (:732-748): the reply carries Command and
+                             the CatchUpLog log_from[i] .. last_committed                        */
+
+/* Prepare bodies to records: from the mpx_peer_frame list mpx_decode_stream[_dev] left (the same
+ * buf, the same offsets), the frames of code MPX_PEER_PREPARE, compacted and in stream order.
+ * The body is 12 bytes in MIN (msgs[i] = {group, Ballot, LeaderId, LastCommitted}) and 13 in
+ * CLASSIC ({Instance, Ballot, LeaderId, ToInfinity}), by mpx_config.mode. group: the Replica the
+ * peer connection belongs to (as mpx_client_conn.group for clients); it fills key in MIN and is
+ * not read in CLASSIC. frame_index[i] = the frame's index in other. Frames of other codes are
+ * skipped. *n_prepares is always complete; nothing is written at or past cap (a capacity of 0 may
+ * come with null arrays). Host form: a Prepare frame outside [0, len) -> MPX_E_INVAL.           */
+int mpx_gather_prepares(mpx_engine* eng, const uint8_t* buf, size_t len,
+                        const mpx_peer_frame* other, size_t n_other, int32_t group,
+                        mpx_prepare_msg* msgs, uint32_t* frame_index, size_t cap,
+                        uint64_t* n_prepares);
+/* device form: its scratch is the PrepareReply encoder's: it needs
+ * mpx_encode_prepare_replies_reserve(n_other, 0, 1) (or any larger reserve) first. d_n_other
+ * (optional, device): min(*d_n_other, n_other) frames are processed, so the call can be captured
+ * right behind mpx_decode_stream_dev. A frame outside [0, len) is reported through the error word
+ * and skipped. d_buf may be read up to len rounded up to 16, never at or past it. Alignment: d_buf
+ * and d_msgs 16 bytes (any other address is rejected with MPX_E_INVAL); d_n_other, d_n_prepares 8;
+ * d_other, d_frame_index 4.                                                                     */
+int mpx_gather_prepares_dev(mpx_engine* eng, const uint8_t* d_buf, size_t len,
+                            const mpx_peer_frame* d_other, size_t n_other,
+                            const uint64_t* d_n_other, int32_t group, mpx_prepare_msg* d_msgs,
+                            uint32_t* d_frame_index, size_t cap, uint64_t* d_n_prepares,
+                            void* stream);
+
+/* handlePrepare for a batch. msgs[n] in contract order: grouped by key ascending, slot order =
+ * arrival order inside a key (mpx_order_records keyed on key gives it; in MIN with inst_base = 0
+ * and n_inst = n_groups). st[n_inst] is read only; groups[n_groups] is in/out. replies:
+ * mpx_prepare_reply[n] in CLASSIC, mpx_prepare_reply_min[n] in MIN, by mpx_config.mode. They mean
+ * what mpx_decode_stream makes them mean, except value_id: the window index of the slot whose Cmds
+ * the reply's Command carries, or MPX_VALUE_KEEP where the reply carries none. Outputs are
+ * slot-aligned with msgs, one entry per message, always written: replies[i], reply_to[i] =
+ * msgs[i].leader_id, effect[i] (MPX_PRH_*) and, in MIN, log_from[i] (null in CLASSIC).
+ *   CLASSIC  D = the group's running default_ballot. st[idx] nil: ok = !(D > ballot), the reply is
+ *            {Instance, ok, D, no commands}; else ok = !(ballot < inst.ballot), {Instance, ok,
+ *            inst.ballot, value_id = idx}. Then, if arg == 1 (TRUE is uint8(1): a byte of 2 raises
+ *            nothing) and ballot > D, D = ballot. Only groups[g].default_ballot is written.
+ *            D moves over the instances of a group in BATCH order (instance ascending), not in
+ *            arrival order: the on-purpose difference INTEGRATION documents for the watermarks.
+ *   MIN      per group, sequentially in batch order: if default_ballot < ballot: ok, default_ballot
+ *            = ballot, leader = leader_id, prepare_oks = 0 and, where gps and peer_commits are
+ *            given, gps[g] = {ballot, 0, 0, ballot, first_g, MPX_VALUE_KEEP; committed_upto and
+ *            triggered untouched} and peer_commits[g * N ..] = first_g (the reference's literal 0).
+ *            crt_instance advances past non-nil slots. committed_upto <= arg: the reply is
+ *            {self_id, crt - 1, ok, default_ballot, committed_upto}, no commands, no log, log_from
+ *            = committed_upto + 1. Otherwise MPX_PRH_LOG: Command is the Cmds of slot committed_upto
+ *            + 1 when crt > committed_upto (value_id = its window index), and the CatchUpLog is the
+ *            instances arg + 1 .. committed_upto: log_from = arg + 1.
+ *            The reference indexes a nil culog at :744 and would panic; the engine builds the range
+ *            that indexing names, the range handlePrepareReply (:936-938) consumes.
+ * Errors: a CLASSIC key outside the window, a MIN crt_instance leaving the group's window, a nil
+ * or out-of-window slot committed_upto + 1 where Command reads it, a catch-up range that leaves
+ * the group's window or holds a nil slot -> MPX_E_NIL_INSTANCE; a MIN key outside [0, n_groups)
+ * -> MPX_E_INVAL; leader_id outside [0, N) -> MPX_E_BAD_ID; order -> MPX_E_INVAL. A message that
+ * raised an error still leaves a reply that encodes safely: no commands, an empty log.
+ * Host form: stages only the span of st the batch touches.                                      */
+int mpx_prepare_handle(mpx_engine* eng, const mpx_prepare_msg* msgs, size_t n,
+                       const mpx_acceptor_state* st, size_t n_inst, int32_t inst_base,
+                       mpx_proposer_group* groups, size_t n_groups, uint32_t ipg,
+                       mpx_group_prep_state* gps, int32_t* peer_commits, void* replies,
+                       int32_t* reply_to, uint8_t* effect, int32_t* log_from);
+/* device form: d_groups (and d_gps, d_peer_commits) updated in place. One kernel, no scratch, no
+ * control words beyond the error word; it captures into a graph. A thread per message; the thread
+ * of a group's first message walks the group's run, so the work is the messages' (plus MIN's crt
+ * advance and the slots of the ranges it names), never the window's. Alignment: d_msgs, d_st,
+ * d_groups, d_gps 16 bytes; d_replies 8 (MIN) / 16 (CLASSIC); d_peer_commits, d_reply_to,
+ * d_log_from 4; d_effect any address.                                                           */
+int mpx_prepare_handle_dev(mpx_engine* eng, const mpx_prepare_msg* d_msgs, size_t n,
+                           const mpx_acceptor_state* d_st, size_t n_inst, int32_t inst_base,
+                           mpx_proposer_group* d_groups, size_t n_groups, uint32_t ipg,
+                           mpx_group_prep_state* d_gps, int32_t* d_peer_commits, void* d_replies,
+                           int32_t* d_reply_to, uint8_t* d_effect, int32_t* d_log_from,
+                           void* stream);
+
+/* one call of mpx_encode_prepare_replies: the handler's outputs and the instance store, named as
+ * mpx_accept_store_batch names it                                                                */
+typedef struct mpx_prepare_reply_batch {
+    const void* replies;           /* mpx_prepare_reply_min[n] (MIN) / mpx_prepare_reply[n]      */
+    const int32_t* reply_to;       /* n: the destination (< 0: skipped)                          */
+    const int32_t* log_from;       /* n, MIN: the log is log_from[i] .. replies[i].last_committed */
+    size_t n;
+    uint32_t n_dest;               /* 1 .. MPX_MAX_REPLICAS                                       */
+    int32_t inst_base;
+    size_t n_inst;
+    const mpx_acceptor_state* st;  /* n_inst (MIN)                                                */
+    const mpx_inst_state* lb;      /* n_inst, optional                                            */
+    const mpx_inst_cmds* inst;     /* n_inst                                                      */
+    const uint8_t* src_op;         /* the command arena, n_src                                    */
+    const int64_t* src_key;
+    const int64_t* src_val;
+    size_t n_src;
+    uint32_t reserved;             /* 0                                                           */
+} mpx_prepare_reply_batch;
+
+/* The frames replyPrepare -> SendMsg writes, little endian, V = binary.PutVarint:
+ *   MIN      [12][Id][Instance][OK u8][Ballot][LastCommitted][V(n)][n x 17 B][V(m)][m Instances]
+ *   CLASSIC  [12][Instance][OK u8][Ballot][V(n)][n x 17 B]
+ * Command is inst[value_id]'s range of the arena; a slot without MPX_IC_HAS_CMDS, or a value_id of
+ * MPX_VALUE_KEEP, marshals as V(0). A log Instance is mpx_encode_accepts_stored's, word for word:
+ * nil exactly when st is nil, Ballot from st, Status from lb where it has one, else from st, Cmds
+ * through inst. m = last_committed - log_from[i] + 1 where that is positive, else 0.
+ * replies[i] goes to destination reply_to[i] (< 0: skipped; >= n_dest: MPX_E_INVAL). out receives,
+ * destination by destination, each destination's frames in array order, back to back: destination
+ * d's run is out[dest_off[d] .. dest_off[d+1]) (dest_off: n_dest + 1 entries, always complete).
+ * Nothing is ever written at or past out_cap; dest_off[n_dest] > out_cap -> MPX_E_INVAL with
+ * dest_off written.
+ * Errors, host form, answered before anything is staged: a value_id other than MPX_VALUE_KEEP
+ * outside [0, n_inst), a log range that leaves the window, a flagged slot a frame reads whose
+ * [first_cmd, first_cmd + n_cmds) leaves [0, n_src) -> MPX_E_INVAL; a nil instance inside a log
+ * range -> MPX_E_NIL_INSTANCE. The host form stages the span of st / lb / inst the frames touch
+ * and, of the arena, only the referenced commands, gathered into a compact copy.                */
+int mpx_encode_prepare_replies(mpx_engine* eng, const mpx_prepare_reply_batch* b, uint8_t* out,
+                               size_t out_cap, uint64_t* dest_off);
+/* scratch for _dev calls of up to max_n replies to up to n_dest destinations over a window of up
+ * to max_n_inst instances, and for mpx_gather_prepares_dev over up to max_n frames (grows only).
+ * The scratch lives in the handle: the family's calls on one handle run in one stream order, and a
+ * larger reserve invalidates graphs captured before it.                                         */
+int mpx_encode_prepare_replies_reserve(mpx_engine* eng, size_t max_n, size_t max_n_inst,
+                                       uint32_t n_dest);
+/* device form: b is a host struct of device pointers. Never allocates or synchronises, needs no
+ * memset on the stream; it captures into a graph. The errors above arrive through the error word;
+ * the instance, command range or log range at fault is sized and encoded as empty, so sizes and
+ * bytes agree and no load leaves the window or the arena. Alignment: replies 8 (MIN) / 16
+ * (CLASSIC); st, lb, inst 16 bytes; src_key, src_val and d_dest_off 8; reply_to, log_from 4;
+ * src_op and d_out any address; any other address is rejected with MPX_E_INVAL.                 */
+int mpx_encode_prepare_replies_dev(mpx_engine* eng, const mpx_prepare_reply_batch* b,
+                                   uint8_t* d_out, size_t out_cap, uint64_t* d_dest_off,
+                                   void* stream);
+
 /* ---- durable-log replay (read side) ----------------------------------
  * bareminpaxos.(*Replica).getDataFromStableStore  src/bareminpaxos/bareminpaxos.go:122-161:
  * the stable store as back-to-back MPX_DURABLE_REC_BYTES records (metadata Ballot, Status,

@@ -53,6 +53,13 @@ class MpxAcceptStoreBatch(C.Structure):
                 ("flags", C.c_uint32), ("alive_mask", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MpxPrepareReplyBatch(C.Structure):
+    _fields_ = [("replies", _p), ("reply_to", _p), ("log_from", _p), ("n", _sz),
+                ("n_dest", C.c_uint32), ("inst_base", C.c_int32), ("n_inst", _sz), ("st", _p),
+                ("lb", _p), ("inst", _p), ("src_op", _p), ("src_key", _p), ("src_val", _p),
+                ("n_src", _sz), ("reserved", C.c_uint32)]
+
+
 class MpxUnmarshalOut(C.Structure):
     _fields_ = [("accepts", _p), ("accept_last_committed", _p), ("accept_cap", _sz),
                 ("commits", _p), ("commit_cap", _sz), ("cmd_off", _p), ("op", _p), ("key", _p),
@@ -220,6 +227,16 @@ SIGNATURES = {
     "mpx_encode_commits": (C.c_int, [_p, C.POINTER(MpxCommitBatch), _p, _sz, _p]),
     "mpx_encode_commits_reserve": (C.c_int, [_p, _sz, _sz]),
     "mpx_encode_commits_dev": (C.c_int, [_p, C.POINTER(MpxCommitBatch), _p, _sz, _p, _p]),
+    "mpx_gather_prepares": (C.c_int, [_p, _p, _sz, _p, _sz, _i32, _p, _p, _sz, _p]),
+    "mpx_gather_prepares_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _i32, _p, _p, _sz, _p, _p]),
+    "mpx_prepare_handle": (C.c_int, [_p, _p, _sz, _p, _sz, _i32, _p, _sz, C.c_uint32, _p, _p, _p,
+                                     _p, _p, _p]),
+    "mpx_prepare_handle_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _i32, _p, _sz, C.c_uint32, _p, _p,
+                                         _p, _p, _p, _p, _p]),
+    "mpx_encode_prepare_replies": (C.c_int, [_p, C.POINTER(MpxPrepareReplyBatch), _p, _sz, _p]),
+    "mpx_encode_prepare_replies_reserve": (C.c_int, [_p, _sz, _sz, C.c_uint32]),
+    "mpx_encode_prepare_replies_dev": (C.c_int, [_p, C.POINTER(MpxPrepareReplyBatch), _p, _sz, _p,
+                                                 _p]),
     "mpx_gather_commit_shorts": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _sz, _p]),
     "mpx_gather_commit_shorts_dev": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _p, _p, _sz, _p,
                                                _p]),

@@ -217,7 +217,7 @@ int mpx_close(mpx_engine* e) {
     for (DevBuf* x : {&e->arena, &e->apply_work, &e->decode_work, &e->stream_work, &e->fan_work,
                       &e->log_work, &e->replay_work, &e->are_work, &e->ab_work, &e->um_work,
                       &e->cm_work, &e->ord_work, &e->cl_work, &e->rp_work, &e->xg_work,
-                      &e->st_work, &e->lr_work, &e->worklist})
+                      &e->st_work, &e->lr_work, &e->pr_work, &e->worklist})
         if (x->p) (void)hipFree(x->p);
     if (e->pin_io.p) (void)hipHostFree(e->pin_io.p);
     if (e->pin_staged.p) (void)hipHostFree(e->pin_staged.p);

@@ -1,6 +1,6 @@
 // engine_host.hpp — the host side's private parts that more than one translation unit of the
 // C-ABI layer needs (engine.cpp, order.cpp, client.cpp, replies.cpp, execute.cpp, store.cpp, record.cpp,
-// accepts_stored.cpp): the handle,
+// accepts_stored.cpp, prepare_handle.cpp): the handle,
 // error reporting, the families' scratch buffers and the staging arena of the host-pointer forms.
 // The command sources of store.cpp and record.cpp (their checks, the pre-check of an item's
 // commands, their staging) are cmd_src_host.hpp's, the host side of the kernels' assemble.hpp.
@@ -46,7 +46,8 @@ struct mpx_engine {
     bool kv_ready = false;
     // the families' scratch: grown by the host forms and the *_reserve calls, never by a _dev form
     mpx_host::DevBuf apply_work, decode_work, stream_work, fan_work, log_work, replay_work,
-        are_work, ab_work, um_work, cm_work, ord_work, cl_work, rp_work, xg_work, st_work, lr_work;
+        are_work, ab_work, um_work, cm_work, ord_work, cl_work, rp_work, xg_work, st_work, lr_work,
+        pr_work;
     size_t um_var_cap = 0, um_log_cap = 0;  // what um_work was last sized for (mpx_unmarshal_frames)
     size_t cm_send_cap = 0, cm_other_cap = 0;  // ... and cm_work (mpx_encode_commits_reserve)
     size_t xg_inst_cap = 0, xg_group_cap = 0;  // ... and xg_work (mpx_execute_gather_reserve)

@@ -223,6 +223,31 @@ hipError_t launch_encode_accepts_stored(
     int mode, int32_t nrep, const mpx_accept_store_batch* b, uint8_t* out, uint64_t out_cap,
     uint64_t* dest_off, void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
 
+// ---- the prepare side (mpx_gather_prepares, mpx_prepare_handle, mpx_encode_prepare_replies;
+// prepare_handle.hip) -------------------------------------------------------------------------
+// The handler is one launch: no scratch, no control words. replies: mpx_prepare_reply_min (MIN) /
+// mpx_prepare_reply (CLASSIC); gps, peer_commits (MIN) and log_from (CLASSIC) may be null.
+hipError_t launch_prepare_handle(
+    int mode, const mpx_prepare_msg* msgs, uint64_t n, const mpx_acceptor_state* st, uint64_t n_inst,
+    int32_t base, mpx_proposer_group* groups, uint64_t n_groups, uint32_t ipg, int32_t nrep,
+    mpx_group_prep_state* gps, int32_t* peer_commits, void* replies, int32_t* reply_to,
+    uint8_t* effect, int32_t* log_from, uint32_t* err, hipStream_t stream);
+// the family's scratch: an encode of n replies to n_dest destinations over n_inst window slots; a
+// gather over n frames fits in it whatever the other two arguments; monotone in each argument
+uint64_t prepare_replies_work_bytes(uint32_t n_dest, uint64_t n, uint64_t n_inst,
+                                    Carver&& c = Carver());
+// b: a host struct of device pointers; nothing is written at or past out + out_cap
+hipError_t launch_encode_prepare_replies(
+    int mode, const mpx_prepare_reply_batch* b, uint8_t* out, uint64_t out_cap, uint64_t* dest_off,
+    void* work, uint64_t work_bytes, uint32_t* err, hipStream_t stream);
+// d_n_other (optional, device): min(*d_n_other, n_other) frames are processed. Never reads buf at
+// or past len rounded up to 16.
+hipError_t launch_gather_prepares(
+    int mode, const uint8_t* buf, uint64_t len, const mpx_peer_frame* other, uint64_t n_other,
+    const uint64_t* d_n_other, int32_t group, mpx_prepare_msg* msgs, uint32_t* frame_index,
+    uint64_t cap, uint64_t* n_prepares, void* work, uint64_t work_bytes, uint32_t* err,
+    hipStream_t stream);
+
 // ---- Accept / Commit / PrepareReply payloads (mpx_unmarshal_frames; unmarshal.hip) ----------
 // Scratch for calls of up to n_var frames carrying up to n_log catch-up instances in total.
 uint64_t unmarshal_work_bytes(uint64_t n_var, uint64_t n_log, Carver&& c = Carver());

@@ -21,6 +21,10 @@ Names and argument meaning follow the reference handlers they replace:
                          updateCommittedUpTo for a commit-only batch
   encode_commits      <- bcastCommit -> SendMsg: the CommitShort / Commit frames per peer
   gather_commit_shorts <- CommitShort.Unmarshal of the frames decode_stream listed
+  gather_prepares     <- Prepare.Unmarshal of the frames decode_stream listed
+  prepare_handle      <- bareminpaxos / paxos  handlePrepare (the follower's half of Phase 1)
+  encode_prepare_replies <- replyPrepare -> SendMsg: the PrepareReply frames per leader
+                         connection, Command and CatchUpLog read from the instance store
   order_records       <- the shim's sort.SliceStable by Instance over the drained connections:
                          the batch order every handler above asks for
   decode_client_streams <- genericsmr.clientListener + Propose.Unmarshal over many connections:
@@ -756,6 +760,126 @@ class Engine:
                                                           d_n_other, d_msgs, d_count,
                                                           d_frame_index, cap, d_n_shorts, stream),
                     "mpx_gather_commit_shorts_dev")
+
+    # ---- the prepare side: Prepare records, handlePrepare, the PrepareReply bytes --------------
+    def _reply_dtype(self):
+        return R.PREPARE_REPLY_MIN if self.mode == R.MODE_MIN else R.PREPARE_REPLY
+
+    def gather_prepares(self, buf, other, group=0, cap=None):
+        """buf: the bytes decode_stream framed; other: its PEER_FRAME records; group: the Replica
+        the connection belongs to (MIN: it fills key). Returns (msgs PREPARE_MSG, frame_index
+        uint32, n_prepares): the Prepare frames in stream order, trimmed to min(n_prepares, cap)."""
+        buf = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else \
+            _c(buf, np.uint8)
+        other = _c(other, R.PEER_FRAME)
+        cap = int((other["code"] == R.PEER_PREPARE).sum()) if cap is None else cap
+        msgs = np.zeros(max(cap, 1), R.PREPARE_MSG)
+        idx = np.zeros(max(cap, 1), np.uint32)
+        ns = np.zeros(1, np.uint64)
+        rc = self.lib.mpx_gather_prepares(self.h, _ptr(buf), len(buf), _ptr(other), len(other),
+                                          group, _ptr(msgs), _ptr(idx), cap, _ptr(ns))
+        self._check(rc, "mpx_gather_prepares")
+        k = min(int(ns[0]), cap)
+        return msgs[:k], idx[:k], int(ns[0])
+
+    def gather_prepares_dev(self, d_buf, n, d_other, n_other, d_n_other, group, d_msgs,
+                            d_frame_index, cap, d_n_prepares, stream=None):
+        self._check(self.lib.mpx_gather_prepares_dev(self.h, d_buf, n, d_other, n_other, d_n_other,
+                                                     group, d_msgs, d_frame_index, cap,
+                                                     d_n_prepares, stream),
+                    "mpx_gather_prepares_dev")
+
+    def prepare_handle(self, msgs, st, groups, inst_base=0, ipg=None, gps=None,
+                       peer_commits=None):
+        """msgs: PREPARE_MSG grouped by key, ascending; st: ACCEPTOR_STATE of the window (read
+        only); groups: PROPOSER_GROUP (copied). gps / peer_commits (MIN, optional, copied): the
+        GROUP_PREP_STATE array and the int32 [G * N] rows a raised ballot resets. Returns a dict:
+        groups, replies (PREPARE_REPLY_MIN or PREPARE_REPLY), reply_to int32, effect uint8,
+        log_from int32 (MIN, else None), gps, peer_commits."""
+        msgs = _c(msgs, R.PREPARE_MSG)
+        st = _c(st, R.ACCEPTOR_STATE)
+        groups = np.array(np.atleast_1d(groups), dtype=R.PROPOSER_GROUP, copy=True)
+        n, G = len(msgs), len(groups)
+        ipg = (len(st) // G if G else 0) if ipg is None else ipg
+        minm = self.mode == R.MODE_MIN
+        if gps is not None:
+            gps = np.array(gps, dtype=R.GROUP_PREP_STATE, copy=True)
+        if peer_commits is not None:
+            peer_commits = np.array(peer_commits, dtype=np.int32, copy=True)
+        rep = np.zeros(max(n, 1), self._reply_dtype())
+        to = np.zeros(max(n, 1), np.int32)
+        eff = np.zeros(max(n, 1), np.uint8)
+        lf = np.zeros(max(n, 1), np.int32) if minm else None
+        rc = self.lib.mpx_prepare_handle(self.h, _ptr(msgs), n, _ptr(st), len(st), inst_base,
+                                         _ptr(groups), G, ipg, _ptr(gps), _ptr(peer_commits),
+                                         _ptr(rep), _ptr(to), _ptr(eff), _ptr(lf))
+        self._check(rc, "mpx_prepare_handle")
+        return {"groups": groups, "replies": rep[:n], "reply_to": to[:n], "effect": eff[:n],
+                "log_from": lf[:n] if minm else None, "gps": gps, "peer_commits": peer_commits}
+
+    def prepare_handle_dev(self, d_msgs, n, d_st, n_inst, inst_base, d_groups, n_groups, ipg,
+                           d_replies, d_reply_to, d_effect, d_log_from=None, d_gps=None,
+                           d_peer_commits=None, stream=None):
+        rc = self.lib.mpx_prepare_handle_dev(self.h, d_msgs, n, d_st, n_inst, inst_base, d_groups,
+                                             n_groups, ipg, d_gps, d_peer_commits, d_replies,
+                                             d_reply_to, d_effect, d_log_from, stream)
+        self._check(rc, "mpx_prepare_handle_dev")
+
+    def encode_prepare_replies(self, replies, reply_to, log_from=None, n_dest=None, inst_base=0,
+                               st=None, lb=None, inst=None, arena=None, out_cap=None):
+        """replies / reply_to / log_from: prepare_handle's outputs; st ACCEPTOR_STATE[n_inst], lb
+        optional INST_STATE[n_inst], inst INST_CMDS[n_inst] and arena (op, key, val) they point
+        into. Returns (bytes uint8, dest_off u64[n_dest+1]): leader d's connection receives
+        out[dest_off[d]:dest_off[d+1]], PrepareReply frames in array order."""
+        replies = _c(replies, self._reply_dtype())
+        reply_to = _c(reply_to, np.int32)
+        n_dest = self.n_replicas if n_dest is None else n_dest
+        keep = [replies, reply_to]
+        b = _lib.MpxPrepareReplyBatch()
+        b.replies, b.reply_to, b.n, b.n_dest = _ptr(replies), _ptr(reply_to), len(replies), n_dest
+        b.inst_base = inst_base
+        if log_from is not None:
+            log_from = _c(log_from, np.int32)
+            keep.append(log_from)
+            b.log_from = _ptr(log_from)
+        if st is not None:
+            st = _c(st, R.ACCEPTOR_STATE)
+            keep.append(st)
+            b.st = _ptr(st)
+        if lb is not None:
+            lb = _c(lb, R.INST_STATE)
+            keep.append(lb)
+            b.lb = _ptr(lb)
+        if inst is not None:
+            inst = _c(inst, R.INST_CMDS)
+            keep.append(inst)
+            b.inst, b.n_inst = _ptr(inst), len(inst)
+        if arena is not None:
+            sop, skey, sval = _c(arena[0], np.uint8), _c(arena[1], np.int64), _c(arena[2], np.int64)
+            keep += [sop, skey, sval]
+            b.src_op, b.src_key, b.src_val, b.n_src = _ptr(sop), _ptr(skey), _ptr(sval), len(sop)
+        if out_cap is None:  # every frame with every instance of the window in its log
+            k = 0
+            if inst is not None and len(inst):
+                k = int(np.where(inst["flags"] & R.IC_HAS_CMDS, inst["n_cmds"], 0).astype(np.int64).sum())
+            out_cap = len(replies) * (28 + 18 * b.n_inst + 2 * 17 * k)
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        off = np.zeros(n_dest + 1, np.uint64)
+        rc = self.lib.mpx_encode_prepare_replies(self.h, C.byref(b), _ptr(out), out_cap, _ptr(off))
+        self._check(rc, "mpx_encode_prepare_replies")
+        del keep
+        return out[:int(off[-1])], off
+
+    def encode_prepare_replies_reserve(self, max_n, max_n_inst, n_dest=None):
+        n_dest = self.n_replicas if n_dest is None else n_dest
+        self._check(self.lib.mpx_encode_prepare_replies_reserve(self.h, max_n, max_n_inst, n_dest),
+                    "mpx_encode_prepare_replies_reserve")
+
+    def encode_prepare_replies_dev(self, batch, d_out, out_cap, d_dest_off, stream=None):
+        """batch: _lib.MpxPrepareReplyBatch of device pointers"""
+        self._check(self.lib.mpx_encode_prepare_replies_dev(self.h, C.byref(batch), d_out, out_cap,
+                                                            d_dest_off, stream),
+                    "mpx_encode_prepare_replies_dev")
 
     # ---- batch assembly: several connections' records as one legal handler batch -------------
     def order_records(self, sources, n_inst, inst_base=0, arrivals=None, arrival_bits=0,

@@ -118,6 +118,16 @@ AB_THRIFTY = 1
 # arrays: ACCEPTOR_STATE (ballot, status), optionally INST_STATE (the status once the tally has
 # committed), INST_CMDS and the command arena they point into (below)
 
+# the prepare side (mpx_gather_prepares / mpx_prepare_handle / mpx_encode_prepare_replies)
+# mpx_prepare_msg  <- minpaxosproto.Prepare / paxosproto.Prepare. key: CLASSIC the Instance, MIN the
+# group of the connection; arg: CLASSIC ToInfinity (the wire byte), MIN LastCommitted
+PREPARE_MSG = np.dtype([("key", "<i4"), ("ballot", "<i4"), ("leader_id", "<i4"), ("arg", "<i4")])
+PRH_OK, PRH_RAISED, PRH_LOG = 1, 2, 4
+# the Prepare frame's body after the code byte, and the PrepareReply frame's fixed head, by mode
+PREPARE_BODY = {MODE_MIN: 12, MODE_CLASSIC: 13}
+PREPARE_REPLY_HEAD = {MODE_MIN: 18, MODE_CLASSIC: 10}
+assert PREPARE_MSG.itemsize == 16
+
 # the commit side (mpx_commit_handle / mpx_encode_commits / mpx_gather_commit_shorts)
 VALUE_KEEP = 0xFFFFFFFF  # value_id of a CommitShort record (no Command; nil Cmds on a nil instance)
 CH_INSTALLED, CH_CMDS, CH_REQUEUE = 1, 2, 4

@@ -133,6 +133,12 @@ int main(int argc, char** argv) {
            SIZE_OF(accepts_stored_work_bytes, 5, x, 1 << 16));
     family("accepts stored (N = 16, 1000 sends, slots)", S, true,
            SIZE_OF(accepts_stored_work_bytes, 16, 1000, x));
+    family("prepare replies (N = 5, replies, 2^16 slots)", S, true,
+           SIZE_OF(prepare_replies_work_bytes, 5, x, 1 << 16));
+    family("prepare replies (N = 16, 1000 replies, slots)", S, true,
+           SIZE_OF(prepare_replies_work_bytes, 16, 1000, x));
+    family("prepare replies (gather: 1, frames, 0)", S, true,
+           SIZE_OF(prepare_replies_work_bytes, 1, x, 0));
     for (const int32_t cap : {1, 8192, 1 << 20, 1 << 24, 1 << 25}) {
         char name[64];
         std::snprintf(name, sizeof(name), "replay (inst_cap %d)", cap);
