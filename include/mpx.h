@@ -1374,7 +1374,9 @@ int mpx_decode_client_streams_dev(mpx_engine* eng, const uint8_t* d_buf, size_t 
  * measurements).
  * Errors, host form, answered before anything is staged: null arguments, an unknown kind or flags,
  * the kind's forbidden or missing arrays, reserved != 0, an eligible slot whose command range
- * leaves [0, n_props) or whose result range leaves [0, n_ret) -> MPX_E_INVAL; with mask given, an
+ * leaves [0, n_props), a selected slot whose result range leaves [0, n_ret) (a slot the mask passes
+ * over reads no result: mpx_execute_gather's ret_first puts an instance that did not execute where
+ * the executed ones before it end, which may be n_ret itself) -> MPX_E_INVAL; with mask given, an
  * eligible slot whose instance is outside the window -> MPX_E_NIL_INSTANCE; n_sends or the total
  * at or above 2^32-1 -> MPX_E_UNSUPPORTED.                                                        */
 #define MPX_RB_FALSE 1u

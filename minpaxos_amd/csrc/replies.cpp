@@ -77,11 +77,6 @@ int mpx_build_replies(mpx_engine* e, const mpx_reply_batch* b, mpx_reply_rec* re
         if (!(x.flags & eligible)) continue;
         if (x.first_cmd > (uint64_t)b->n_props || x.n_cmds > (uint64_t)b->n_props - x.first_cmd)
             return fail(e, MPX_E_INVAL, "a slot's command range leaves [0, n_props)");
-        if (b->kind == MPX_RB_EXECUTED) {
-            const uint64_t rf = b->ret_first ? b->ret_first[s] : x.first_cmd;
-            if (rf > (uint64_t)b->n_ret || x.n_cmds > (uint64_t)b->n_ret - rf)
-                return fail(e, MPX_E_INVAL, "a slot's result range leaves [0, n_ret)");
-        }
         bool selected = true;
         if (b->mask) {
             const int64_t rel = (int64_t)x.instance - b->inst_base;
@@ -90,6 +85,13 @@ int mpx_build_replies(mpx_engine* e, const mpx_reply_batch* b, mpx_reply_rec* re
             selected = b->mask[rel] != 0;
         }
         if (!selected) continue;
+        // only a selected slot reads results: an instance that did not execute in this call has none,
+        // and mpx_execute_gather's ret_first puts it wherever the executed ones before it end
+        if (b->kind == MPX_RB_EXECUTED) {
+            const uint64_t rf = b->ret_first ? b->ret_first[s] : x.first_cmd;
+            if (rf > (uint64_t)b->n_ret || x.n_cmds > (uint64_t)b->n_ret - rf)
+                return fail(e, MPX_E_INVAL, "a selected slot's result range leaves [0, n_ret)");
+        }
         total += refusals && !(x.flags & MPX_PH_NOT_LEADER) ? std::min(x.n_cmds, 1u) : x.n_cmds;
         if (total >= 0xFFFFFFFFull) return fail(e, MPX_E_UNSUPPORTED, "2^32-1 replies or more");
     }

@@ -59,7 +59,8 @@ struct RbSlot {
     uint32_t err;  // kErr* bits
 };
 
-// Slot s judged: eligibility by kind, the ranges, the window, the mask; its mpx_commit_send
+// Slot s judged: eligibility by kind, the command range, the window, the mask, a selected slot's
+// result range; its mpx_commit_send
 // written when the call asks for them.
 __device__ __forceinline__ RbSlot rb_slot(const RbArgs& a, uint64_t s) {
     const uint4* p = reinterpret_cast<const uint4*>(a.sends + s);
@@ -72,15 +73,15 @@ __device__ __forceinline__ RbSlot rb_slot(const RbArgs& a, uint64_t s) {
     RbSlot r{0, false, 0};
     if (eligible) {
         if (first > a.n_props || n > a.n_props - first) r.err |= kErrInval;
-        if (a.kind == MPX_RB_EXECUTED) {
-            const uint64_t rf = a.ret_first ? a.ret_first[s] : first;
-            if (rf > a.n_ret || n > a.n_ret - rf) r.err |= kErrInval;
-        }
         r.sel = true;
         if (a.mask) {
             const int64_t rel = (int64_t)(int32_t)h0.x - a.inst_base;
             if (rel < 0 || (uint64_t)rel >= a.n_inst) r.err |= kErrNil;
             else r.sel = a.mask[rel] != 0;
+        }
+        if (r.sel && a.kind == MPX_RB_EXECUTED) {  // only a selected slot reads results
+            const uint64_t rf = a.ret_first ? a.ret_first[s] : first;
+            if (rf > a.n_ret || n > a.n_ret - rf) r.err |= kErrInval;
         }
         if (r.err) r.sel = false;
         if (r.sel) r.cnt = refusals && !(flags & MPX_PH_NOT_LEADER) ? min(n, 1u) : n;

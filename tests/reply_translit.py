@@ -104,10 +104,6 @@ def _slot_fault(kind, s, x, n_props, n_ret, ret_first, mask, inst_base):
     code = R.OK
     if first > n_props or n > n_props - first:
         code = R.E_INVAL
-    if kind == R.RB_EXECUTED:
-        rf = first if ret_first is None else int(ret_first[s])
-        if rf > n_ret or n > n_ret - rf:
-            code = R.E_INVAL
     selected = True
     if mask is not None:
         rel = int(x["instance"]) - inst_base
@@ -115,6 +111,10 @@ def _slot_fault(kind, s, x, n_props, n_ret, ret_first, mask, inst_base):
             code = code or R.E_NIL_INSTANCE
             return code, False
         selected = bool(mask[rel])
+    if kind == R.RB_EXECUTED and selected:   # only a selected slot reads results
+        rf = first if ret_first is None else int(ret_first[s])
+        if rf > n_ret or n > n_ret - rf:
+            code = R.E_INVAL
     return code, selected
 
 

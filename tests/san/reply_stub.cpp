@@ -48,14 +48,14 @@ hipError_t launch_build_replies(const mpx_reply_batch* b, mpx_reply_rec* recs, u
             uint32_t bits = 0;
             if (x.first_cmd > b->n_props || x.n_cmds > b->n_props - x.first_cmd) bits |= kErrInval;
             const uint64_t rf = b->ret_first ? b->ret_first[s] : x.first_cmd;
-            if (b->kind == MPX_RB_EXECUTED && (rf > b->n_ret || x.n_cmds > b->n_ret - rf))
-                bits |= kErrInval;
             sel = true;
             if (b->mask) {
                 const int64_t rel = (int64_t)x.instance - b->inst_base;
                 if (rel < 0 || (uint64_t)rel >= b->n_inst) bits |= kErrNil;
                 else sel = b->mask[rel] != 0;
             }
+            if (sel && b->kind == MPX_RB_EXECUTED && (rf > b->n_ret || x.n_cmds > b->n_ret - rf))
+                bits |= kErrInval;  // only a selected slot reads results
             if (bits) {
                 *err |= bits;
                 sel = false;

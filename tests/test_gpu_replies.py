@@ -239,6 +239,31 @@ def test_ret_first(eng):
 
 
 @pytest.mark.gpu
+def test_a_slot_the_mask_passes_over_reads_no_result(eng):
+    """execute_gather -> build_replies(EXECUTED) over slots kept from earlier turns: ret_first puts
+    an instance that did not execute where the executed ones before it end, for the last slots
+    n_ret itself, so their result range leaves ret. The mask passes over them and they read no
+    result: no fault, host and _dev form (the closed-loop test found the two contracts at odds,
+    DESIGN §25). Selected, the same slot is the fault it was."""
+    counts, base = [3, 2, 4], 100
+    inst = np.zeros(3, R.INST_CMDS)
+    inst["first_cmd"], inst["n_cmds"], inst["flags"] = [0, 3, 5], counts, R.IC_HAS_CMDS
+    case = mk_case(R.RB_EXECUTED, counts, base=base)
+    cmds = (np.ones(9, np.uint8), np.arange(9, dtype=np.int64), np.arange(9, dtype=np.int64))
+    x = eng.execute_gather(inst, [base], [base - 1], cmds, base, 3, sends=case["sends"])
+    assert x["mask"].tolist() == [1, 0, 0] and x["ret_first"].tolist() == [0, 3, 3] and len(x["op"]) == 3
+    case.update(mask=x["mask"], ret_first=x["ret_first"], ret=case["ret"][:3])
+    want = check(eng, case)
+    assert want["recs"]["value"].tolist() == [1, 4, 7] and int(want["res"]["n_slots"]) == 1
+    bad = dict(case, mask=np.array([1, 0, 1], np.uint8))
+    assert T.build_replies(**bad)["code"] == R.E_INVAL
+    assert _code(run_host, eng, bad, 7, False, True) == R.E_INVAL
+    got = run_dev(eng, bad, 7, False, True)
+    assert got[3] == R.E_INVAL and got[0]["value"].tolist() == [1, 4, 7]
+    check(eng, mk_case(R.RB_DECIDED, [2, 3]))
+
+
+@pytest.mark.gpu
 def test_commit_sends_with_and_without_recs(eng):
     counts = [5, 0, 1200, 3, 17]
     for kind in (R.RB_DECIDED, R.RB_EXECUTED):

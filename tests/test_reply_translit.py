@@ -77,6 +77,26 @@ def test_faulty_slots_by_form():
     assert T.build_replies(R.RB_EXECUTED, sends, meta, ret=ret, ret_first=rf)["code"] == R.E_INVAL
 
 
+def test_a_slot_the_mask_passes_over_reads_no_result():
+    """execute_gather's ret_first puts an instance that did not execute where the executed ones
+    before it end (the last slots: at n_ret itself); build_replies(EXECUTED) judges the result range
+    of the slots it selects only"""
+    import execute_translit as X
+    sends = T.mk_sends([(100, 4, R.PH_ACCEPT, 0, 3), (101, 4, R.PH_ACCEPT, 3, 2), (102, 4, R.PH_ACCEPT, 5, 4)])
+    meta = T.mk_meta([(j, j, j % 2) for j in range(9)])
+    inst = np.zeros(3, R.INST_CMDS)
+    inst["first_cmd"], inst["n_cmds"], inst["flags"] = [0, 3, 5], [3, 2, 4], R.IC_HAS_CMDS
+    cmds = (np.ones(9, np.uint8), np.arange(9), np.arange(9))
+    x = X.execute_gather(inst, [100], [99], cmds, 100, 3, sends=sends)
+    assert x["mask"].tolist() == [1, 0, 0] and x["ret_first"].tolist() == [0, 3, 3]
+    ret = np.array([11, 12, 13], np.int64)
+    for dev in (False, True):
+        got = T.build_replies(R.RB_EXECUTED, sends, meta, x["mask"], 100, ret, x["ret_first"], dev=dev)
+        assert got["code"] == R.OK and got["recs"]["value"].tolist() == [11, 12, 13]
+    assert T.build_replies(R.RB_EXECUTED, sends, meta, np.array([1, 0, 1], np.uint8), 100, ret,
+                           x["ret_first"])["code"] == R.E_INVAL
+
+
 def test_fuzz_generator_reaches_every_slot_kind():
     """over the fuzz seeds each slot kind is at least 0.02 of the slots"""
     census = {}
