@@ -1,7 +1,8 @@
 // frames.hpp — the building blocks the frame encoders share (logenc.hip, acceptor.hip,
 // proposer.hip, commit.hip): wire bytes into an LDS image, the offset scans' functors, the
 // window emitters' piece bookkeeping, bcast's ring walk, and the send-major partition's steps.
-// Plain inlined functions: every caller keeps its own frame layout, loops and launchers.
+// Plain inlined functions: every caller keeps its own frame layout, loops and launchers (the three
+// encoders of frames with a catch-up log share theirs one level up, in catchup.hpp).
 // All workgroup-wide helpers are for kFrBlock threads and are called by every thread, with its
 // index t: the caller has it in a register.
 #pragma once

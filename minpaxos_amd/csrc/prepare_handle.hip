@@ -19,7 +19,7 @@
 //            Commands, V(m), m Instances (:100-124: Ballot, Status, V(k), k Commands)
 //   CLASSIC  paxosprotomarsh.go:126-150     Instance, OK, Ballot, V(n), n Commands
 // with Command and the CatchUpLog read from the instance store as accepts_stored.hip reads its
-// log (st / lb / mpx_inst_cmds / the command arena). The steps are that unit's:
+// log (st / lb / mpx_inst_cmds / the command arena: catchup.hpp's StoreLog):
 //   1. MIN: two window scans: lcoff (the commands a slot marshals: none when unflagged, nil or
 //      out of the arena, so sizes and bytes agree and no load leaves [0, n_src)) and log_off (the
 //      slots' Instance.Marshal sizes). A log range's bytes are a difference of two prefix sums.
@@ -27,12 +27,13 @@
 //      != q; a destination-major scan in place: frame_off[] and dest_off[] (the stable partition
 //      by reply_to falls out of the item order).
 //   3. k_pr_emit: a workgroup per 8 KB output window: the holder search, then per 256 items the
-//      pieces that overlap the window (the header, Command's commands, log headers, log
-//      commands), dealt over the threads by a workgroup scan, ORed into the LDS image, stored as
-//      16-byte vectors.
-// Nothing is materialised per frame. The building blocks are frames.hpp's.
+//      pieces that overlap the window (the header, Command's commands, log headers, log commands),
+//      dealt over the threads by a workgroup scan, ORed into the LDS image, stored as 16-byte
+//      vectors.
+// Nothing is materialised per frame. The scans, the window loop and the scratch are catchup.hpp's;
+// here: the gather, the handler, the PrepareReply frame (pr_frame) and its head (PrPolicy).
 #include "common.hpp"
-#include "frames.hpp"
+#include "catchup.hpp"
 #include "kernels.hpp"
 #include "scan.hpp"
 
@@ -272,12 +273,6 @@ hipError_t launch_prepare_handle(int mode, const mpx_prepare_msg* msgs, uint64_t
 
 // ---- PrepareReply frames ---------------------------------------------------------------------------
 namespace {
-constexpr int kPrBlock = kFrBlock;
-constexpr int kPrWaves = kPrBlock / kWave;
-constexpr int kPrWindowVec = 2;  // 16-byte vectors per thread in one output window
-constexpr int kPrWindow = kPrBlock * 16 * kPrWindowVec;  // bytes of one output window
-constexpr int kPrWords = kPrWindow / 4;               // ... as the dwords of its LDS image
-constexpr int kPrGrid = 8192;             // workgroups at most (windows are walked grid-stride)
 constexpr uint32_t kPrHeadMin = 18u;      // the code byte, Id, Instance, OK, Ballot, LastCommitted
 constexpr uint32_t kPrHeadClassic = 10u;  // the code byte, Instance, OK, Ballot
 
@@ -301,61 +296,14 @@ struct PrArgs {
     const uint64_t* log_off;  // scratch (MIN): log_off[i] = log bytes of window slots [0, i)
     uint32_t min, head;
 };
-
-// a slot's Cmds as the store names them
-struct PrCmds {
-    uint64_t first;
-    uint32_t n, flags;
-    __device__ __forceinline__ bool in_arena(uint64_t n_src) const {
-        return first <= n_src && n <= n_src - first;
-    }
-};
-__device__ __forceinline__ PrCmds pr_cmds(const mpx_inst_cmds* inst, uint64_t i) {
-    const int4 x = reinterpret_cast<const int4*>(inst)[i];
-    return {(uint64_t)(uint32_t)x.x | ((uint64_t)(uint32_t)x.y << 32), (uint32_t)x.z, (uint32_t)x.w};
-}
-
-// scan 1: the commands window slot i marshals inside a log (the synthetic lcoff)
-struct PrCmdCount {
-    const mpx_acceptor_state* st;
-    const mpx_inst_cmds* inst;
-    uint64_t n_src;
-    __device__ __forceinline__ uint64_t operator()(uint64_t i) const {
-        const PrCmds c = pr_cmds(inst, i);
-        const int32_t status = st[i].status;
-        const bool has = (c.flags & MPX_IC_HAS_CMDS) && status != MPX_STATUS_NIL && c.in_arena(n_src);
-        return has ? c.n : 0u;
-    }
-};
-// scan 2: log bytes of window slot i (Instance.Marshal)
-struct PrRecBytes {
-    const uint64_t* coff;
-    __device__ __forceinline__ uint64_t operator()(uint64_t i) const {
-        const uint64_t nc = coff[i + 1] - coff[i];
-        return 8u + varint_len(nc) + 17 * nc;
-    }
-};
-// both leave n + 1 offsets, the leading zero included (no launch for it)
-struct PrOffOut {
-    uint64_t* off;
-    __device__ __forceinline__ void operator()(uint64_t i, uint64_t s, uint64_t b) const {
-        if (i == 0) off[0] = 0;
-        off[i + 1] = s + b;
-    }
-};
-
-// frame of reply s to destination q (bytes == 0: none)
-struct PrFrame {
-    uint64_t bytes;
-    uint64_t first_cmd;
-    uint64_t lo, L0;  // first log record (window index), its log_off
-    uint32_t n, m;    // len(Command), len(CatchUpLog)
+struct PrHead {
     int32_t id, inst, ballot, lc;
     uint32_t ok;
 };
 
-__device__ __forceinline__ PrFrame pr_frame(const PrArgs& a, uint64_t item, uint32_t* err) {
-    PrFrame f;
+// frame of reply s to destination q (bytes == 0: none)
+__device__ __forceinline__ CuFrame<PrHead> pr_frame(const PrArgs& a, uint64_t item, uint32_t* err) {
+    CuFrame<PrHead> f;
     f.bytes = 0;
     const uint64_t q = item / a.n, s = item - q * a.n;
     const int32_t to = a.reply_to[s];
@@ -368,20 +316,20 @@ __device__ __forceinline__ PrFrame pr_frame(const PrArgs& a, uint64_t item, uint
     if (a.min) {
         const int2* r = reinterpret_cast<const int2*>(a.replies) + 3 * s;
         const int2 r0 = r[0], r1 = r[1], r2 = r[2];
-        f.id = r0.x;
-        f.inst = r0.y;
-        f.ballot = r1.x;
-        f.lc = r1.y;
-        f.ok = (uint32_t)r2.x;
+        f.head.id = r0.x;
+        f.head.inst = r0.y;
+        f.head.ballot = r1.x;
+        f.head.lc = r1.y;
+        f.head.ok = (uint32_t)r2.x;
         vid = (uint32_t)r2.y;
         lc = (int64_t)r1.y - a.base;
     } else {
         const int4 r = reinterpret_cast<const int4*>(a.replies)[s];
-        f.id = 0;
-        f.inst = r.x;
-        f.ballot = r.y;
-        f.lc = 0;
-        f.ok = (uint32_t)r.z;
+        f.head.id = 0;
+        f.head.inst = r.x;
+        f.head.ballot = r.y;
+        f.head.lc = 0;
+        f.head.ok = (uint32_t)r.z;
         vid = (uint32_t)r.w;
     }
     f.n = f.m = 0;
@@ -390,7 +338,7 @@ __device__ __forceinline__ PrFrame pr_frame(const PrArgs& a, uint64_t item, uint
         if ((uint64_t)vid >= a.n_inst || !a.inst) {
             raise_err(err, kErrInval);
         } else {
-            const PrCmds c = pr_cmds(a.inst, vid);
+            const StoreCmds c = store_cmds(a.inst, vid);
             if (c.flags & MPX_IC_HAS_CMDS) {
                 if (c.in_arena(a.n_src)) {
                     f.n = c.n;
@@ -419,241 +367,57 @@ __device__ __forceinline__ PrFrame pr_frame(const PrArgs& a, uint64_t item, uint
     return f;
 }
 
-// what a window needs of one frame, left in LDS by the item's thread for the piece threads
-struct PrPiece {
-    int64_t start;       // frame start - window start
-    uint64_t cmd0;       // first Command entry overlapping the window (arena index)
-    uint64_t lcmd0;      // first log command overlapping the window (lcoff's index)
-    uint64_t L0;         // log_off of the frame's first log record
-    uint64_t i0;         // first log record overlapping the window (window index)
-    uint32_t j0;         // cmd0's position in the frame's Command slice
-    uint32_t n, m;
-    uint32_t c_new, c_inst, c_log;  // pieces: Command's commands, log headers, log commands
-    int32_t id, inst, ballot, lc;
-    uint32_t ok;
+// catchup.hpp's policy: Command's commands come from the arena, as the log's do; the frame was
+// sized with Command's whole range inside the arena
+template <bool MIN>
+struct PrPolicy {
+    static constexpr bool kLog = MIN;
+    static constexpr uint32_t kHead = MIN ? kPrHeadMin : kPrHeadClassic;
+    using Head = PrHead;
+    const PrArgs& a;
+    __device__ __forceinline__ const uint64_t* log_off() const { return a.log_off; }
+    __device__ __forceinline__ StoreLog log() const {
+        return {a.st, a.lb, a.inst, a.sop, a.skey, a.sval, a.n_src, a.lcoff};
+    }
+    __device__ __forceinline__ CuFrame<Head> frame(uint64_t item, uint32_t* err) const {
+        return pr_frame(a, item, err);
+    }
+    __device__ __forceinline__ void put_head(uint32_t (&h)[6], const Head& F) const {
+        h[0] = MPX_PEER_PREPARE_REPLY;
+        if (MIN) {
+            put32(h, 1, (uint32_t)F.id);
+            put32(h, 5, (uint32_t)F.inst);
+            h[2] |= (F.ok & 0xFFu) << 8;  // byte 9
+            put32(h, 10, (uint32_t)F.ballot);
+            put32(h, 14, (uint32_t)F.lc);
+        } else {
+            put32(h, 1, (uint32_t)F.inst);
+            h[1] |= (F.ok & 0xFFu) << 8;  // byte 5
+            put32(h, 6, (uint32_t)F.ballot);
+        }
+    }
+    __device__ __forceinline__ Cmd3 cmd(uint64_t j) const {
+        return {a.sop[j], (uint64_t)a.skey[j], (uint64_t)a.sval[j]};
+    }
 };
-
-// the len bytes of V(n) (len <= 8) as one little-endian word
-__device__ __forceinline__ uint64_t varint_word(uint64_t n, uint32_t len) {
-    uint64_t w = 0;
-    for (uint32_t x = 0; x < len; ++x) w |= (uint64_t)varint_byte(n, x) << (8 * x);
-    return w;
-}
-// v's four bytes into the header words h at byte offset at
-template <int ND>
-__device__ __forceinline__ void put32(uint32_t (&h)[ND], uint32_t at, uint32_t v) {
-    const uint32_t sh = 8u * (at & 3u);
-    h[at >> 2] |= v << sh;
-    if (sh) h[(at >> 2) + 1] |= v >> (32u - sh);
-}
 }  // namespace
 
-__global__ __launch_bounds__(kPrBlock) void k_pr_sizes(PrArgs a, uint64_t n_items,
+__global__ __launch_bounds__(kFrBlock) void k_pr_sizes(PrArgs a, uint64_t n_items,
                                                        uint64_t* __restrict__ size, uint32_t* err) {
-    const uint64_t i = (uint64_t)blockIdx.x * kPrBlock + threadIdx.x;
-    if (i < n_items) size[i] = pr_frame(a, i, err).bytes;
+    catchup_sizes(PrPolicy<true>{a}, n_items, size, err);  // (pr_frame reads the mode from a)
 }
 
 // (a kernel per mode: the head's length is then a constant, and the header words stay in
 // registers; as one kernel with a run-time head they went to 32 bytes of scratch per lane)
 template <bool MIN>
-__global__ __launch_bounds__(kPrBlock) void k_pr_emit(PrArgs a, const uint64_t* __restrict__ frame_off,
+__global__ __launch_bounds__(kFrBlock) void k_pr_emit(PrArgs a, const uint64_t* __restrict__ frame_off,
                                                       uint64_t n_items, uint8_t* __restrict__ out,
                                                       uint64_t out_cap, uint32_t* err) {
-    constexpr uint32_t kHead = MIN ? kPrHeadMin : kPrHeadClassic;
-    __shared__ PrPiece fi[kPrBlock];
-    __shared__ uint32_t poff[kPrBlock + 1];
-    __shared__ uint32_t wtot[kPrWaves];
-    __shared__ __attribute__((aligned(16))) uint32_t W[kPrWindow / 4];
-    const int t = threadIdx.x;
-    const uint64_t total = frame_off[n_items];
-    const uint64_t lim = total < out_cap ? total : out_cap;  // nothing at or past out_cap
-    for (uint64_t b0 = (uint64_t)blockIdx.x * kPrWindow; b0 < lim;
-         b0 += (uint64_t)gridDim.x * kPrWindow) {
-        const uint64_t b1 = b0 + kPrWindow < lim ? b0 + kPrWindow : lim;
-#pragma unroll
-        for (int v = 0; v < kPrWindowVec; ++v)
-            reinterpret_cast<uint4*>(W)[t + v * kPrBlock] = make_uint4(0, 0, 0, 0);
-        const uint64_t lo = holder(frame_off, n_items, 0, b0, t);  // the item holding byte b0
-        for (uint64_t c0 = lo;; c0 += kPrBlock) {
-            const uint64_t i = c0 + t;
-            uint32_t np = 0;
-            uint64_t fs = 0, fe = 0;
-            if (i < n_items) {
-                fs = frame_off[i];
-                fe = frame_off[i + 1];
-            }
-            if (fe > fs && fs < b1 && fe > b0) {
-                const PrFrame f = pr_frame(a, i, nullptr);  // (k_pr_sizes raised the errors)
-                PrPiece p;
-                p.start = (int64_t)fs - (int64_t)b0;
-                p.n = f.n;
-                p.m = f.m;
-                p.id = f.id;
-                p.inst = f.inst;
-                p.ballot = f.ballot;
-                p.lc = f.lc;
-                p.ok = f.ok;
-                p.L0 = f.L0;
-                const uint64_t cs = fs + kHead + varint_len(f.n);  // the Command slice
-                const CmdSpan sp = cmd_span(cs, b0, b1);
-                const uint64_t jl = sp.lo, jh = sp.hi < f.n ? sp.hi : f.n;
-                p.j0 = (uint32_t)jl;
-                p.cmd0 = f.first_cmd + jl;
-                p.c_new = jh > jl ? (uint32_t)(jh - jl) : 0u;
-                p.c_inst = p.c_log = 0;
-                p.i0 = 0;
-                p.lcmd0 = 0;
-                if (f.m) {
-                    // the window in the log's byte coordinates: [x0, x1) of [L0, L1)
-                    const uint64_t ls = cs + 17ull * f.n + varint_len(f.m);
-                    const uint64_t L1 = f.L0 + (fe - ls);
-                    const uint64_t x0 = b0 > ls ? f.L0 + (b0 - ls) : f.L0;
-                    const uint64_t x1 = b1 > ls ? (f.L0 + (b1 - ls) < L1 ? f.L0 + (b1 - ls) : L1)
-                                                : f.L0;
-                    if (x0 < x1) {
-                        // i0 = last record with log_off <= x0, i1 = last with log_off < x1
-                        uint64_t ra = f.lo, rb = f.lo + f.m;
-                        while (rb - ra > 1) {
-                            const uint64_t mid = (ra + rb) >> 1;
-                            if (a.log_off[mid] <= x0) ra = mid; else rb = mid;
-                        }
-                        const uint64_t i0 = ra;
-                        rb = f.lo + f.m;
-                        while (rb - ra > 1) {
-                            const uint64_t mid = (ra + rb) >> 1;
-                            if (a.log_off[mid] < x1) ra = mid; else rb = mid;
-                        }
-                        const uint64_t i1 = ra;
-                        p.i0 = i0;
-                        p.c_inst = (uint32_t)(i1 - i0 + 1);
-                        const uint64_t ca0 = a.lcoff[i0], ca1 = a.lcoff[i0 + 1];
-                        const uint64_t cb0 = a.lcoff[i1], cb1 = a.lcoff[i1 + 1];
-                        const uint64_t cs0 = a.log_off[i0 + 1] - 17 * (ca1 - ca0);
-                        const uint64_t cs1 = a.log_off[i1 + 1] - 17 * (cb1 - cb0);
-                        const uint64_t la = ca0 + cmd_span(cs0, x0, x1).lo;
-                        uint64_t lh = cb0 + cmd_span(cs1, x0, x1).hi;
-                        lh = lh < cb1 ? lh : cb1;
-                        p.lcmd0 = la;
-                        p.c_log = lh > la ? (uint32_t)(lh - la) : 0u;
-                    }
-                }
-                fi[t] = p;
-                np = 1u + p.c_new + p.c_inst + p.c_log;
-            }
-            const uint32_t pieces = piece_scan(np, poff, wtot, t);
-            for (uint32_t p = t; p < pieces; p += kPrBlock) {
-                const uint32_t fa = piece_item(poff, p);
-                const PrPiece& F = fi[fa];
-                uint32_t k = p - poff[fa];
-                const uint32_t vn = varint_len(F.n);
-                const int64_t cs = F.start + kHead + vn;
-                if (k == 0) {  // the header and V(n); MIN: V(m) behind the commands
-                    uint32_t h[6] = {MPX_PEER_PREPARE_REPLY, 0u, 0u, 0u, 0u, 0u};
-                    if (MIN) {
-                        put32(h, 1, (uint32_t)F.id);
-                        put32(h, 5, (uint32_t)F.inst);
-                        h[2] |= (F.ok & 0xFFu) << 8;  // byte 9
-                        put32(h, 10, (uint32_t)F.ballot);
-                        put32(h, 14, (uint32_t)F.lc);
-                    } else {
-                        put32(h, 1, (uint32_t)F.inst);
-                        h[1] |= (F.ok & 0xFFu) << 8;  // byte 5
-                        put32(h, 6, (uint32_t)F.ballot);
-                    }
-                    // V(n) behind the head: at most 5 bytes, shifted as one 64-bit word (no
-                    // indexed store into h: it stays in registers)
-                    const uint64_t vw = varint_word(F.n, vn) << (8 * (kHead & 3));
-                    h[kHead >> 2] |= (uint32_t)vw;
-                    h[(kHead >> 2) + 1] |= (uint32_t)(vw >> 32);
-                    image_or<kPrWords>(W, F.start, h, kHead + vn);
-                    if (MIN) {
-                        const uint32_t vm = varint_len(F.m);
-                        const uint64_t mw = varint_word(F.m, vm);
-                        const uint32_t v[2] = {(uint32_t)mw, (uint32_t)(mw >> 32)};
-                        image_or<kPrWords>(W, cs + 17ll * F.n, v, vm);
-                    }
-                    continue;
-                }
-                --k;
-                if (k < F.c_new) {  // one of Command's commands: the frame was sized with its
-                                    // whole range inside the arena
-                    const uint64_t j = F.cmd0 + k;
-                    image_or_cmd<kPrWords>(W, cs + 17ll * (F.j0 + k), a.sop[j], (uint64_t)a.skey[j],
-                                           (uint64_t)a.sval[j]);
-                    continue;
-                }
-                k -= F.c_new;
-                // the CatchUpLog starts at ls; a record's bytes sit at ls + log_off[i] - L0
-                const int64_t ls = cs + 17ll * F.n + varint_len(F.m);
-                if (k < F.c_inst) {  // a log record's header: Ballot, Status, V(len(Cmds))
-                    const uint64_t r = F.i0 + k;
-                    const int4 s = reinterpret_cast<const int4*>(a.st)[r];  // status, ballot
-                    const PrCmds c = pr_cmds(a.inst, r);
-                    int32_t status = s.x;
-                    if (a.lb) {  // the tally commits in lb alone
-                        const int32_t ls_ = a.lb[r].status;
-                        status = ls_ != MPX_STATUS_NIL ? ls_ : status;
-                    }
-                    // what the host form answers before it stages; the record is then emitted
-                    // with no commands, as it was sized
-                    if (s.x == MPX_STATUS_NIL) raise_err(err, kErrNil);
-                    else if ((c.flags & MPX_IC_HAS_CMDS) && !c.in_arena(a.n_src))
-                        raise_err(err, kErrInval);
-                    const uint64_t nc = a.lcoff[r + 1] - a.lcoff[r];
-                    const uint32_t vk = varint_len(nc);
-                    const uint64_t kw = varint_word(nc, vk);
-                    const uint32_t h[5] = {(uint32_t)s.y, (uint32_t)status, (uint32_t)kw,
-                                           (uint32_t)(kw >> 32), 0u};
-                    image_or<kPrWords>(W, ls + (int64_t)(a.log_off[r] - F.L0), h, 8 + vk);
-                    continue;
-                }
-                k -= F.c_inst;
-                {  // a log command: its record is the last of the window's with lcoff <= j
-                    const uint64_t j = F.lcmd0 + k;
-                    uint64_t ra = F.i0, rb = F.i0 + F.c_inst;
-                    while (rb - ra > 1) {
-                        const uint64_t mid = (ra + rb) >> 1;
-                        if (a.lcoff[mid] <= j) ra = mid; else rb = mid;
-                    }
-                    const uint64_t c0r = a.lcoff[ra], c1r = a.lcoff[ra + 1];
-                    const uint64_t csr = a.log_off[ra + 1] - 17 * (c1r - c0r);
-                    // lcoff counts a record's commands only where its whole range is in the
-                    // arena, so first_cmd + (j - c0r) < n_src
-                    const uint64_t at = a.inst[ra].first_cmd + (j - c0r);
-                    image_or_cmd<kPrWords>(W, ls + (int64_t)(csr - F.L0) + 17ll * (int64_t)(j - c0r),
-                                           a.sop[at], (uint64_t)a.skey[at], (uint64_t)a.sval[at]);
-                }
-            }
-            const uint64_t nx = c0 + kPrBlock;
-            if (nx >= n_items || frame_off[nx] >= b1) break;  // (uniform)
-            __syncthreads();  // fi and poff are rewritten by the next chunk
-        }
-        __syncthreads();
-        window_store(W, (uint32_t)(b1 - b0), out + b0, t);
-        __syncthreads();  // the next window zeroes W
-    }
+    catchup_emit(PrPolicy<MIN>{a}, frame_off, n_items, out, out_cap, err);
 }
 
-namespace {
-struct PrWork {
-    uint64_t* log_off;    // n_inst + 1
-    uint64_t* lcoff;      // n_inst + 1
-    uint64_t* frame_off;  // n_dest * n + 1
-    uint64_t* scan_tmp;   // for the largest of the scans, the gather's among them
-    PrWork(Carver& c, uint32_t n_dest, uint64_t n, uint64_t n_inst) {
-        const uint64_t items = (uint64_t)n_dest * n;
-        log_off = c.take<uint64_t>(n_inst + 1);
-        lcoff = c.take<uint64_t>(n_inst + 1);
-        frame_off = c.take<uint64_t>(items + 1);
-        const uint64_t big = items > n_inst ? items : n_inst;
-        scan_tmp = (uint64_t*)c.take<char>(scan_scratch_bytes<uint64_t>(big ? big : 1));
-    }
-};
-}  // namespace
-
 uint64_t prepare_replies_work_bytes(uint32_t n_dest, uint64_t n, uint64_t n_inst, Carver&& c) {
-    return PrWork(c, n_dest, n, n_inst), c.bytes();
+    return CatchupWork(c, n_dest, n, n_inst, true), c.bytes();
 }
 
 hipError_t launch_encode_prepare_replies(int mode, const mpx_prepare_reply_batch* b, uint8_t* out,
@@ -668,47 +432,32 @@ hipError_t launch_encode_prepare_replies(int mode, const mpx_prepare_reply_batch
     }
     const bool min = mode == MPX_MODE_MIN;
     Carver c(work);
-    const PrWork w(c, b->n_dest, b->n, b->n_inst);
+    const CatchupWork w(c, b->n_dest, b->n, b->n_inst, true);
     if (work_bytes < c.bytes()) return hipErrorInvalidValue;
-    PrArgs a;
-    a.replies = b->replies;
-    a.reply_to = b->reply_to;
-    a.log_from = b->log_from;
-    a.n = b->n;
-    a.n_dest = b->n_dest;
-    a.base = b->inst_base;
-    a.n_inst = b->n_inst;
-    a.st = b->st;
-    a.lb = b->lb;
-    a.inst = b->inst;
-    a.sop = b->src_op;
-    a.skey = b->src_key;
-    a.sval = b->src_val;
-    a.n_src = b->n_src;
-    a.lcoff = w.lcoff;
-    a.log_off = w.log_off;
-    a.min = min ? 1u : 0u;
-    a.head = min ? kPrHeadMin : kPrHeadClassic;
-    hipError_t r;
+    const PrArgs a{b->replies,
+                   b->reply_to,
+                   b->log_from,
+                   b->n,
+                   b->n_dest,
+                   b->inst_base,
+                   b->n_inst,
+                   b->st,
+                   b->lb,
+                   b->inst,
+                   b->src_op,
+                   b->src_key,
+                   b->src_val,
+                   b->n_src,
+                   w.lcoff,
+                   w.log_off,
+                   min ? 1u : 0u,
+                   min ? kPrHeadMin : kPrHeadClassic};
     if (min && b->n_inst) {  // (CLASSIC frames carry no log)
-        r = device_scan(PrCmdCount{b->st, b->inst, b->n_src}, PrOffOut{w.lcoff}, b->n_inst,
-                        ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
-        if (r != hipSuccess) return r;
-        r = device_scan(PrRecBytes{w.lcoff}, PrOffOut{w.log_off}, b->n_inst, ScanSum64{},
-                        (uint64_t)0, w.scan_tmp, stream);
+        const hipError_t r = store_log_offsets(b->st, b->inst, b->n_src, b->n_inst, w, stream);
         if (r != hipSuccess) return r;
     }
-    k_pr_sizes<<<(unsigned)((items + kPrBlock - 1) / kPrBlock), kPrBlock, 0, stream>>>(
-        a, items, w.frame_off, err);
-    r = device_scan(SizeIn{w.frame_off}, FrameOffOut{w.frame_off, dest_off, a.n, items}, items,
-                    ScanSum64{}, (uint64_t)0, w.scan_tmp, stream);
-    if (r != hipSuccess) return r;
-    const uint64_t windows = (out_cap + kPrWindow - 1) / kPrWindow;
-    if (!windows) return hipSuccess;
-    const unsigned grid = (unsigned)(windows < (uint64_t)kPrGrid ? windows : (uint64_t)kPrGrid);
-    if (min) k_pr_emit<true><<<grid, kPrBlock, 0, stream>>>(a, w.frame_off, items, out, out_cap, err);
-    else k_pr_emit<false><<<grid, kPrBlock, 0, stream>>>(a, w.frame_off, items, out, out_cap, err);
-    return hipGetLastError();
+    return catchup_run(k_pr_sizes, min ? k_pr_emit<true> : k_pr_emit<false>, a, w, b->n, items, out,
+                       out_cap, dest_off, err, stream);
 }
 
 hipError_t launch_gather_prepares(int mode, const uint8_t* buf, uint64_t len,
@@ -723,7 +472,7 @@ hipError_t launch_gather_prepares(int mode, const uint8_t* buf, uint64_t len,
         return hipGetLastError();
     }
     Carver c(work);
-    const PrWork w(c, 1, n_other, 0);
+    const CatchupWork w(c, 1, n_other, 0, true);
     if (work_bytes < c.bytes()) return hipErrorInvalidValue;
     return device_scan(GpIn{other, d_n_other, n_other},
                        GpOut{buf, len, other, msgs, frame_index, cap, n_other, n_prepares, err,

@@ -319,6 +319,40 @@ def partition(frames, reply_to, n_dest):
     return np.frombuffer(b"".join(b"".join(x) for x in per), np.uint8), off
 
 
+
+# ---- the window-boundary cases -------------------------------------------------------------------
+def one_reply_case(counts, n_own, seed):
+    """run_batch's arguments for one MIN Prepare to one group whose reply carries a log of
+    len(counts) records (record i with counts[i] commands, every other empty one unflagged: Cmds ==
+    nil marshals as V(0) too) and a Command of n_own commands"""
+    rng = np.random.default_rng(seed)
+    m = len(counts)
+    big = dict(enumerate(counts))
+    big[m], big[m + 1] = n_own, 1
+    st, lb, inst, arena = make_store(rng, 1, m + 4, 0, [m + 2], lb_kind=1, big=big)
+    inst["flags"][[i for i in range(1, m, 2) if counts[i] == 0]] = 0
+    groups = np.zeros(1, R.PROPOSER_GROUP)
+    groups[0] = (7, 0, 0, 2, 0, m - 1, (0, 0))
+    msgs = np.zeros(1, R.PREPARE_MSG)
+    msgs[0] = (0, 9, 1, -1)
+    return dict(msgs=msgs, groups=groups, st=st, inst_base=0, ipg=m + 4, lb=lb, inst=inst,
+                arena=arena)
+
+
+def boundary_case(d):
+    """one MIN PrepareReply frame whose log record z + 1 has its header at byte 8192 + d: the
+    18-byte head, V(2), Command's two commands and V(m) ahead of the log, then the records of
+    proposer_translit.boundary_counts. Returns (arguments, that record's index)."""
+    from proposer_translit import WINDOW, boundary_counts
+    used = boundary_counts(WINDOW + d, 18 + 1 + 34 + 1)
+    return one_reply_case(used, 2, 7300 + d), len(used) - 2
+
+
+def command_straddle_case():
+    """one MIN PrepareReply frame whose Command slice lies across byte 8192 (482 commands behind 18
+    + V(482) bytes: command 480 is bytes 8180 .. 8196), then a log of three records"""
+    return one_reply_case([2, 0, 1], 482, 7400)
+
 # ---- the fuzz generator --------------------------------------------------------------------------
 FUZZ_SEEDS = list(range(24))
 MIN_BRANCHES = ("raised", "not_raised", "no_log", "log", "command")

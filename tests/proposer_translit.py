@@ -386,6 +386,60 @@ def mk_log(rng, counts, nil_at=()):
     return (rec, coff) + mk_cmds(rng, int(k.sum()))
 
 
+
+# ---- the window-boundary sweep -------------------------------------------------------------------
+WINDOW = 8192
+SWEEP = range(-30, 3)
+
+
+def log_starts(frame, head):
+    """walk a MIN frame (head bytes, V(n), n Commands, V(m), m Instances): the offsets at which its
+    log's record headers and its log's commands start"""
+    def varint(pos):
+        u, k = 0, 0
+        while True:
+            x = frame[pos + k]
+            u |= (x & 0x7F) << (7 * k)
+            k += 1
+            if x < 0x80:
+                return u >> 1, pos + k
+    n, pos = varint(head)
+    m, pos = varint(pos + 17 * n)
+    recs, cmds = [], []
+    for _ in range(m):
+        recs.append(pos)
+        k, pos = varint(pos + 8)
+        cmds += [pos + 17 * j for j in range(k)]
+        pos += 17 * k
+    assert pos == len(frame)
+    return recs, cmds
+
+
+def boundary_counts(T, fixed):
+    """the command counts of a log whose record under test starts at byte T of a frame with `fixed`
+    bytes ahead of the log's first record: z records of 9 bytes, one of 10 + 17 k0, the record
+    under test (3 commands), one more (2)"""
+    z = next(z for z in range(17) if (T - fixed - 10 - 9 * z) % 17 == 0)
+    k0 = (T - fixed - 10 - 9 * z) // 17
+    assert k0 >= 64 and z + 3 < 64  # V(k0) of two bytes, V(m) of one
+    return [0] * z + [k0, 3, 2]
+
+
+def boundary_case(d):
+    """encode_accepts' arguments for one MIN frame (2 replicas, to peer 1) whose catch-up record
+    z + 1 has its header at byte 8192 + d: 17 + V(0) + V(m) ahead of the log, the record's first
+    command at 8192 + d + 9, the record before it ending with a command at 8192 + d - 17. Returns
+    (arguments, that record's index)."""
+    used = boundary_counts(WINDOW + d, 19)
+    rng = np.random.default_rng(900 + d)
+    base, ipg = 50, len(used) + 1
+    inst, lc = base + len(used), base + len(used) - 1
+    a = dict(sends=mk_sends([(inst, 16, lc, R.PH_ACCEPT, 0, 0)]),
+             groups=mk_groups([(16, 0, 0, 2, inst + 1, lc)]), cmds=mk_cmds(rng, 0), inst_base=base,
+             ipg=ipg, peer_commits=np.full((1, 2), base - 1, np.int32),
+             log=mk_log(rng, used + [None]))
+    return a, len(used) - 2
+
 # ---- the fuzz generator --------------------------------------------------------------------------
 FUZZ_SEEDS = list(range(24))
 BRANCHES = {R.MODE_MIN: ("not_leader_id", "not_leader_oks", "advance", "refused", "accept"),

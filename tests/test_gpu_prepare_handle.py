@@ -208,6 +208,35 @@ def test_command_counts_and_a_frame_longer_than_a_window(mk_engine, mode):
     assert n_cmds == [0, 1, 63, 64, 500]
 
 
+# ---- the window boundary -----------------------------------------------------------------------------
+@pytest.mark.parametrize("d", range(-30, 3))
+def test_record_header_and_command_at_every_byte_around_the_window_boundary(mk_engine, d):
+    """test_gpu_accepts_stored.py's sweep for a MIN PrepareReply frame: an 18-byte head and the
+    frame's own Command slice (2 commands) ahead of the log, the header of log record k at byte
+    8192 + d, its first command at 8192 + d + 9, the record before it ending with a command at
+    8192 + d - 17 (T.boundary_case; test_prepare_handle_translit.py checks where its inputs put the
+    headers and the commands)"""
+    a, k = T.boundary_case(d)
+    want = check(mk_engine(2, MIN), MIN, 2, a)
+    frame, at = want["frames"][0], WINDOW + d
+    status = int(a["lb"]["status"][k]) if int(a["lb"]["status"][k]) != T.NIL else int(a["st"]["status"][k])
+    head = np.array([a["st"]["ballot"][k], status], "<i4").tobytes() + b"\x06"
+    assert frame[at:at + 9] == head and len(frame) == at + 9 + 51 + 9 + 34
+    c = int(a["inst"]["first_cmd"][k])
+    assert frame[at + 9:at + 26] == T.command_marshal(tuple(int(x[c]) for x in a["arena"]))
+
+
+def test_command_slice_across_the_window_boundary(mk_engine):
+    """the frame's own Command slice (482 commands from the arena) lies across byte 8192, a log of
+    three records behind it; both forms"""
+    a = T.command_straddle_case()
+    want = check(mk_engine(2, MIN), MIN, 2, a)
+    frame = want["frames"][0]
+    c = int(a["inst"]["first_cmd"][3]) + 480
+    assert 18 + 2 + 17 * 480 < WINDOW < 18 + 2 + 17 * 481 < len(frame)
+    assert frame[8180:8197] == T.command_marshal(tuple(int(x[c]) for x in a["arena"]))
+
+
 @pytest.mark.parametrize("log", [0, 1, 64])
 def test_log_lengths_min(mk_engine, log):
     a = big_case(MIN, counts=(2, 0, 3), log=log, ipg=72, seed=log)

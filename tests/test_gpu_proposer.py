@@ -348,6 +348,21 @@ def test_enc_frames_ending_around_a_window_boundary(mk_engine, mode, end):
     assert end in ends and len(w_out) > WINDOW + 1
 
 
+@pytest.mark.parametrize("d", P.SWEEP)
+def test_enc_record_header_and_command_at_every_byte_around_the_window_boundary(mk_engine, d):
+    """the dense MIN encoder on one frame whose catch-up record header starts at byte 8192 + d, the
+    log in log_recs / log_cmd_off / log_op..: test_gpu_accepts_stored.py's sweep (P.boundary_case;
+    test_proposer_translit.py checks where its inputs put the headers and the commands)"""
+    a, k = P.boundary_case(d)
+    _, _, per = check_enc(mk_engine(2, MIN), MIN, 2, a, decode=d % 8 == 0)
+    frame, T = per[1][0], WINDOW + d
+    lrec, lcoff, lop, lkey, lval = a["log"]
+    c = int(lcoff[k])
+    head = np.array([lrec["ballot"][k], lrec["status"][k]], "<i4").tobytes() + b"\x06"
+    assert frame[T:T + 9] == head and len(frame) == T + 9 + 51 + 9 + 34
+    assert frame[T + 9:T + 26] == P.command_marshal(int(lop[c]), int(lkey[c]), int(lval[c]))
+
+
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_enc_300_groups_many_frames_per_window(mk_engine, mode):
     """300 groups led by differing replicas; small frames, so a window holds over 100 of them and

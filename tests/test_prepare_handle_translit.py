@@ -96,3 +96,28 @@ def test_out_of_order_and_panics():
     with pytest.raises(T.GoPanic) as e:
         T.run_batch(mode, 3, **dict(kw, msgs=np.array([(0, 0x20, 3, 9)], R.PREPARE_MSG)))
     assert e.value.code == R.E_BAD_ID
+
+
+def test_boundary_sweep_inputs_sit_on_the_window_boundary():
+    """the GPU sweep (test_gpu_prepare_handle.py) is only as good as its inputs: walked through the
+    transliteration's frames, case d has the header of the record under test at byte 8192 + d, and
+    over the sweep d = -30 .. 2 a record header starts on every byte of 8192 - 30 .. 8192 + 2 (the
+    sweep's own range: the neighbouring headers are 60 bytes and more away) and a log command on
+    every byte of 8192 - 47 .. 8192 + 11; the straddle case has a Command entry across byte 8192"""
+    import proposer_translit as P
+    heads, cmds = set(), set()
+    for d in P.SWEEP:
+        a, k = T.boundary_case(d)
+        want = T.run_batch(R.MODE_MIN, 2, **a)
+        assert len(want["frames"]) == 1 and want["census"] == dict(raised=1, log=1, command=1)
+        recs, starts = P.log_starts(want["frames"][0], 18)
+        assert recs[k] == P.WINDOW + d and len(want["frames"][0]) > P.WINDOW
+        heads.update(recs)
+        cmds.update(starts)
+    assert heads >= set(range(P.WINDOW - 30, P.WINDOW + 3))
+    assert cmds >= set(range(P.WINDOW - 47, P.WINDOW + 12))
+    frame = T.run_batch(R.MODE_MIN, 2, **T.command_straddle_case())["frames"][0]
+    own = [18 + 2 + 17 * j for j in range(482)]
+    assert any(s < P.WINDOW < s + 17 for s in own)
+    recs, _ = P.log_starts(frame, 18)
+    assert recs[0] == own[-1] + 17 + 1 and len(recs) == 3

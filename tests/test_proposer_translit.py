@@ -313,3 +313,22 @@ def test_fuzz_generator_reaches_every_branch(mode):
         kf = {k: kinds[k] / frames for k in P.CATCHUP_KINDS}
         print("catch-up fractions of frames:", kf, "frames", frames)
         assert min(kf.values()) >= 0.02, kf
+
+
+def test_boundary_sweep_inputs_sit_on_the_window_boundary():
+    """the GPU sweep (test_gpu_proposer.py) is only as good as its inputs: walked through the
+    transliteration's frames, case d has the header of the record under test at byte 8192 + d, and
+    over the sweep d = -30 .. 2 a record header starts on every byte of 8192 - 30 .. 8192 + 2 (the
+    sweep's own range: the neighbouring headers are 60 bytes and more away) and a log command on
+    every byte of 8192 - 47 .. 8192 + 11"""
+    heads, cmds = set(), set()
+    for d in P.SWEEP:
+        a, k = P.boundary_case(d)
+        _, _, per = P.encode_accepts(MIN, 2, want_frames=True, **a)
+        assert not per[0] and len(per[1]) == 1
+        recs, starts = P.log_starts(per[1][0], 17)
+        assert recs[k] == P.WINDOW + d and len(per[1][0]) > P.WINDOW
+        heads.update(recs)
+        cmds.update(starts)
+    assert heads >= set(range(P.WINDOW - 30, P.WINDOW + 3))
+    assert cmds >= set(range(P.WINDOW - 47, P.WINDOW + 12))
